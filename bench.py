@@ -1,7 +1,20 @@
 #!/usr/bin/env python
 """Headline benchmark of the hot path on the HIP device.
 
-    python bench.py --gpus N --steps K --warmup W [--config ddim|decode|c4] [--batch B] [--repeats R]
+    python bench.py --gpus N --steps K --warmup W [--config ddim|decode|c4] [--batch B] [--repeats R] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times K steps once (`--repeats` defaults to 1, 3 under `--full`), writes the
+outputs if asked and prints the headline line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (the
+milliseconds of one timed step) and the run's configuration.  Everything else - the per-kernel roofline pass, the side legs
+(batch 8, the other 16-bit type, stock PyTorch-ROCm, the switch-off variants), the decode leg and measured job of the ddim
+line, `parity` and `cpu_baseline` - runs only with `--full` (the `--no-*` options switch single legs off there).
+
+`--dump-outputs DIR`: after the timed steps, what the timed path's LAST step returned is written as DIR/<name>.npy (float32,
+float64 stays float64): ddim / c4 `sample` and `pred_xstart` of the last DDIM step, decode / c4 `primitives` (the
+latents_to_primitives result).  At most 64 MB in all: a larger array is cut to a fixed, seeded sample of its rows (the
+leading dimensions flattened).  Inputs and weights are seeded, so two builds run with the same arguments can be compared
+file for file (rank 0's outputs only).
 
 --config ddim (default): metric = DiT denoise-steps/s.  A "step" is one DDIM iteration on one batch of synthetic input:
   `forward_with_cfg` (effective batch 2B: cond + uncond) through the 28-block PrimX DiT-XL plus the fused diffusion
@@ -21,11 +34,11 @@ process group really has N ranks and that its GPU exists, and the line reports `
 ms/step and `weight_broadcast_bytes`.  `--dry-run` stops after the rendezvous (gloo when there is no GPU: the launcher's
 CPU test).
 
-The default (ddim) line also carries the rest of the metric OUTSIDE the headline's timed region: `decode` (the VAE leg
-on this GPU: ms, samples/s, its own roofline / cpu_baseline / parity) and `samples_per_s_measured` (a whole 25-step
-DDIM loop + decode of the sample, timed end to end, median of R) - `value` stays the denoise-steps/s of K steps.
+With `--full` the default (ddim) line also carries the rest of the metric OUTSIDE the headline's timed region: `decode`
+(the VAE leg on this GPU: ms, samples/s, its own roofline / cpu_baseline / parity) and `samples_per_s_measured` (a whole
+25-step DDIM loop + decode of the sample, timed end to end, median of R) - `value` stays the denoise-steps/s of K steps.
 
-Prints ONE JSON line on rank 0: the contract fields + `roofline` (dominant kernel BY SHAPE, algorithmic FLOPs /
+Prints ONE JSON line on rank 0: the contract fields, and with `--full` `roofline` (dominant kernel BY SHAPE, algorithmic FLOPs /
 HIP-event launch time vs the 2.5 PFLOP/s dense fp16 MFMA peak) + `cpu_baseline` (the CPU oracle - a port of the
 reference algorithm - timed on this host on a bounded sample of the same step) + `parity` (the benchmarked model's own
 output against the fp32 golden of the REAL reference at the full 28-block configuration, and against the fp32 oracle
@@ -82,6 +95,13 @@ def step_stream(diffusion, model, x, kw):
             yield out
 
 
+def host_threads(want: int) -> int:
+    """`want` CPU threads, capped by the CPUs this process may run on and by OMP_NUM_THREADS when that is set."""
+    n = min(want, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(omp)) if omp.isdigit() and int(omp) > 0 else n)
+
+
 def cpu_baseline_ddim(n_prim: int, budget_blocks: int = 28, threads: int = 32):
     """The CPU oracle (oracle/dit_ref.py, fp32 - the port of the reference algorithm, NOT the reference's own modules: /root/reference
     does not exist on the GPU box) on a bounded sample: ONE whole CFG step (effective batch 2) of the full model - all 28 blocks, ~20 s
@@ -93,7 +113,7 @@ def cpu_baseline_ddim(n_prim: int, budget_blocks: int = 28, threads: int = 32):
     x = synth.tensor(WEIGHT_SEED, "xl_c2.x", (1, n_prim, 68))
     y = synth.tensor(WEIGHT_SEED, "xl_c2.y", (1, L_COND, 768))
     t = torch.tensor([800])
-    torch.set_num_threads(min(threads, os.cpu_count() or 1))   # 32 is the measured optimum on the 256-core GPU-box host
+    torch.set_num_threads(host_threads(threads))   # 32 is the measured optimum on a 256-core host
     with torch.no_grad():
         t0 = time.perf_counter()
         out = dit_ref.dit_forward_with_cfg(sd, x, t, y, 16, 6.0)
@@ -110,7 +130,7 @@ def cpu_baseline_decode(vae_sd, n_prims: int = 96, threads: int = 32):
     """oracle/vae_ref.py (fp32 port of VAE.decode) on a bounded sample of primitives; samples/s = prims/s / 2048."""
     from oracle import synth, vae_ref
     z = synth.tensor(WEIGHT_SEED, "bench.vae.z", (n_prims, 1, 4, 4, 4))
-    torch.set_num_threads(min(threads, os.cpu_count() or 1))
+    torch.set_num_threads(host_threads(threads))
     with torch.no_grad():
         vae_ref.vae_decode(vae_sd, z[:8])
         t0 = time.perf_counter()
@@ -167,6 +187,34 @@ def torch_rocm_reference(model, x, y, dt, dev, batches=(1, 8), iters: int = 4):
     finally:
         dit_ref.attention_core = keep
         torch.cuda.empty_cache()
+    return rec
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(outdir: str, arrays: dict) -> dict:
+    """--dump-outputs: `arrays` (name -> tensor) as outdir/<name>.npy, float32 (float64 stays float64).  Arrays are taken in order;
+    one that no longer fits the budget left is cut to a fixed, seeded sample of its rows (leading dimensions flattened, last
+    dimension kept, rows in ascending order).  Returns {name: {"shape", "stored_shape", "dtype"}} for the result line."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    left, rec = DUMP_BUDGET_BYTES, {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        shape = list(t.shape)
+        flat = t.reshape(-1, shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        row_bytes = flat.shape[1] * flat.element_size()
+        left -= 1024                                               # the .npy header
+        keep = min(flat.shape[0], max(0, left) // row_bytes)
+        if keep < flat.shape[0]:
+            idx = torch.randperm(flat.shape[0], generator=torch.Generator().manual_seed(1234))[:keep].sort().values
+            t = flat.index_select(0, idx.to(flat.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+        rec[name] = {"shape": shape, "stored_shape": list(a.shape), "dtype": str(a.dtype)}
     return rec
 
 
@@ -324,7 +372,7 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of K steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed repeats of K steps; the median is reported (default 1, --full: 3)")
     ap.add_argument("--config", default="ddim", choices=["ddim", "decode", "c4"])
     ap.add_argument("--batch", type=int, default=None, help="user samples per GPU (default 1; c4: 8)")
     ap.add_argument("--n-prim", type=int, default=2048)
@@ -337,7 +385,15 @@ def main() -> None:
     ap.add_argument("--no-decode-leg", action="store_true", help="ddim: skip the decode sub-record and the measured 25-step samples/s")
     ap.add_argument("--no-side-legs", action="store_true", help="ddim at batch 1: skip the `batch8` and `bf16` sub-records")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous only: print the ranks that met (launcher check; gloo without a GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg outside the headline: roofline, side legs, decode leg + job, parity, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
@@ -390,7 +446,7 @@ def main() -> None:
         wbytes = broadcast_packed_(model, dt, 0)                  # RCCL: the packed 16-bit blob (N > 1)
         torch.cuda.synchronize()
         wb_ms = 1e3 * (time.perf_counter() - tb0) if wbytes else 0.0
-    decode_leg = args.config == "ddim" and not args.no_decode_leg
+    decode_leg = args.full and args.config == "ddim" and not args.no_decode_leg
     if args.config in ("decode", "c4") or decode_leg:
         from oracle import synth
         with torch.device(dev):
@@ -438,6 +494,14 @@ def main() -> None:
         assert torch.isfinite(last["out"]["sample"]).all(), "non-finite sample"
     else:
         assert torch.isfinite(last_dec["out"]).all(), "non-finite decode"
+    # --dump-outputs: the last timed step's results, copied to the host before any other leg runs (written after the c4 decode)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        if args.config in ("ddim", "c4"):
+            dump = {k: last["out"][k].detach().cpu() for k in ("sample", "pred_xstart") if k in last["out"]}
+        else:
+            dump = {"primitives": last_dec["out"].detach().cpu()}
+    final_sample = last["out"]["sample"].clone() if args.config == "c4" else None
     # what a SCALE record can be audited with: the ranks that really took part (all_gather over the process group, not the
     # launcher's word), every rank's own median ms per step, the weight broadcast's wall time
     ranks_seen = [[rank, local, torch.cuda.get_device_name(dev)]]
@@ -457,7 +521,7 @@ def main() -> None:
     # Roofline leg: HIP events around every MFMA-kernel launch (ops._timed, on the launch stream) over a SEPARATE pass of the
     # same K steps, right after the timed ones (same process, buffers and clocks).
     prof = None
-    if not args.no_kernel_events and rank == 0:
+    if args.full and not args.no_kernel_events and rank == 0:
         ops.PROFILE = []
         run_steps(args.steps)
         torch.cuda.synchronize()
@@ -467,7 +531,7 @@ def main() -> None:
     # Opt-in exact algebra, reported NEXT TO the headline, never as it: the same K steps with the
     # step-invariant cross-attention K / V projections computed once per conditioning tensor (DiT.reuse_cond_kv).
     reuse = None
-    if args.config == "ddim" and not args.reuse_cond_kv and rank == 0 and world == 1:
+    if args.full and args.config == "ddim" and not args.reuse_cond_kv and rank == 0 and world == 1:
         model.reuse_cond_kv = True
         run_steps(args.warmup)
         el, _ = timed_repeats(run_steps, args.steps, max(1, args.repeats), 1, dist, dev)
@@ -483,7 +547,7 @@ def main() -> None:
     # The same K steps with the unconditional half's conditioning rows projected and read EXPANDED (DiT.dedup_null_kv = False): what
     # the headline's de-duplication of `null_cond_embedding.expand_as(y)` saves, for the record.
     expanded = None
-    if args.config == "ddim" and rank == 0 and world == 1 and getattr(model, "dedup_null_kv", False):
+    if args.full and args.config == "ddim" and rank == 0 and world == 1 and getattr(model, "dedup_null_kv", False):
         model.dedup_null_kv = False
         run_steps(args.warmup)
         el, _ = timed_repeats(run_steps, args.steps, max(1, args.repeats), 1, dist, dev)
@@ -498,7 +562,7 @@ def main() -> None:
     # The same K steps with the LayerNorm fold off (DiT.fold_ln = False: 85 LayerNorm launches per forward instead of 2): what the
     # fold saves, for the record (it changes rounding points, not accuracy: tests/test_hip_fold.py, tests/test_hip_fullconfig.py).
     unfolded = None
-    if (args.config == "ddim" and rank == 0 and world == 1 and not args.no_side_legs and getattr(model, "fold_ln", False)
+    if (args.full and args.config == "ddim" and rank == 0 and world == 1 and not args.no_side_legs and getattr(model, "fold_ln", False)
             and model._fold_ok(2 * B * N, N)):
         model.fold_ln = False
         run_steps(args.warmup)
@@ -513,7 +577,7 @@ def main() -> None:
     # The same K steps with the conditioning K / V projection as ONE batched launch per forward (DiT.kv_ride = False) instead of riding on
     # the qkv launches' idle CUs (round 6, ABI 25): what the riders save, for the record (bit-identical samples).
     batched_kv = None
-    if (args.config == "ddim" and rank == 0 and world == 1 and not args.no_side_legs and not args.reuse_cond_kv
+    if (args.full and args.config == "ddim" and rank == 0 and world == 1 and not args.no_side_legs and not args.reuse_cond_kv
             and getattr(model, "kv_ride", False) and getattr(model, "fold_ln", False) and model._fold_ok(2 * B * N, N)):
         model.kv_ride = False
         run_steps(args.warmup)
@@ -532,7 +596,7 @@ def main() -> None:
     side = {}
     # At N > 1 the `batch8` leg runs on EVERY rank (barrier on both sides, MAX over ranks, value = whole job) - the configs[2] shape
     # of a SCALE record; the bf16 and stock-PyTorch legs stay single-GPU context.
-    if args.config == "ddim" and B == 1 and N == 2048 and not args.no_side_legs and not args.reuse_cond_kv:
+    if args.full and args.config == "ddim" and B == 1 and N == 2048 and not args.no_side_legs and not args.reuse_cond_kv:
         def side_leg(bs, sdt, k):
             g2 = torch.Generator().manual_seed(77 + rank)
             xs = x if bs == 1 else torch.randn(bs, N, 68, generator=g2).to(dev)
@@ -613,16 +677,19 @@ def main() -> None:
     # c4: the decode leg, timed separately (median of R)
     decode_s = None
     if args.config == "c4":
-        pipeline.latents_to_primitives(last["out"]["sample"], vae, mean, std)
+        pipeline.latents_to_primitives(final_sample, vae, mean, std)
         dl = []
         for _ in range(max(1, args.repeats)):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            rp = pipeline.latents_to_primitives(last["out"]["sample"], vae, mean, std)
+            rp = pipeline.latents_to_primitives(final_sample, vae, mean, std)
             torch.cuda.synchronize()
             dl.append(time.perf_counter() - t0)
         assert rp.shape == (B, N, 3076) and torch.isfinite(rp).all()
         decode_s = statistics.median(dl)
+        if dump is not None:
+            dump["primitives"] = rp.detach().cpu()
+    dumped = dump_outputs(args.dump_outputs, dump) if dump is not None else None
 
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
@@ -709,6 +776,8 @@ def main() -> None:
         if args.config in ("ddim", "c4"):
             res["ln_in_gemm_tail"] = {"enabled": bool(getattr(model, "fuse_ln", False) and getattr(model, "ln_in_kernel", False)),
                                       "sync_timeouts": ops.ln_sync_timeouts()}
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if prof:
             res["roofline"], res["kernels"] = kernel_report(prof, args.steps, traffic_file(), ev_over)
         if dleg:
@@ -717,7 +786,7 @@ def main() -> None:
             res["measured_job"] = {k: dleg[k] for k in ("job_ms", "job_repeats_ms", "job")}
 
         # ------------------------------------------------------------------ parity of the benchmarked model + CPU baseline
-        if world == 1 and args.config == "ddim" and not args.no_parity and N == 2048:
+        if args.full and world == 1 and args.config == "ddim" and not args.no_parity and N == 2048:
             parity = {}
             gfile = os.path.join(ROOT, "tests", "golden", "xl_c2.npz")
             if os.path.exists(gfile) and B == 1:
@@ -731,7 +800,7 @@ def main() -> None:
                 parity["rel_l2_vs_reference_fp32_28_blocks"] = float((got - ref).norm() / ref.norm())
                 parity["reference"] = "tests/golden/xl_c2.npz: forward_with_cfg of the REAL reference (fp32, all 28 blocks) on these weights and inputs"
             res["parity"] = parity
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.config == "ddim":
                 rec, ref, (sd14, xc, yc, tc, nb) = cpu_baseline_ddim(N)
                 res["cpu_baseline"] = rec

@@ -210,7 +210,21 @@ def gen_vae(vae_mod):
                         shapes=np.array([str(tuple(sd[k].shape)) for k in sorted(sd.keys())]))
 
 
+def gen_t_emb(dit_mod):
+    """The reference's sinusoidal timestep embedding, run with MKL_CBWR=COMPATIBLE: torch's CPU exp / cos / sin go through MKL's
+    vector math, whose default code path - and so the last bits - depends on the host CPU; in this mode MKL takes the same path
+    on every x86 CPU, so tests/test_oracle_golden.py::test_timestep_embedding can stay bit-exact on any host."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "run through main() (or with MKL_CBWR=COMPATIBLE)"
+    t = torch.tensor([0, 1, 40, 500, 960, 999])
+    with torch.no_grad():
+        emb = dit_mod.TimestepEmbedder.timestep_embedding(t, 256).numpy()
+    np.savez_compressed(os.path.join(HERE, "t_emb.npz"), t=t.numpy(), t_emb_freq=emb, mkl_cbwr=np.array("COMPATIBLE"))
+
+
 def main():
+    if sys.argv[1:] == ["--t-emb"]:
+        gen_t_emb(ref_import.load()[0])
+        return
     torch.manual_seed(0)
     torch.set_num_threads(8)
     dit_mod, vae_mod, diffusion_pkg, att_mod = ref_import.load()
@@ -221,6 +235,8 @@ def main():
     gen_dinov2()
     gen_primsdf()
     gen_vae(vae_mod)
+    import subprocess                  # MKL reads MKL_CBWR when it loads: a process of its own
+    subprocess.run([sys.executable, os.path.abspath(__file__), "--t-emb"], env={**os.environ, "MKL_CBWR": "COMPATIBLE"}, check=True)
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(*argv, env_extra=None, timeout=300):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")   # the CPU / gloo path on a GPU box too (1 GPU cannot seat 2 ranks)
     env.update(env_extra or {})
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, env=env,
                           timeout=timeout, cwd=ROOT)
@@ -80,3 +81,30 @@ def test_kernel_report_corrects_the_event_readings(tmp_path):
     assert abs(roof["kernels_sum_ms_per_step"] - (4 * 0.047 + 2 * 0.002 + 2 * 0.027) / 2) < 1e-12
     assert abs(roof["kernels_sum_ms_per_step_raw"] - (4 * 0.050 + 2 * 0.004 + 2 * 0.030) / 2) < 1e-12
     assert roof["traffic"] is None and abs(roof["achieved"] - 1e9 / 0.047e-3 / 1e12) < 1e-9
+
+
+def test_dump_outputs_stay_in_budget_and_float(tmp_path):
+    """`--dump-outputs`: every array lands as DIR/<name>.npy in float32 (float64 kept), a small one whole, one that does not fit
+    the 64 MB left as a seeded sample of its rows - the same rows in every run - and all files together stay within 64 MB."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(5)
+    arrays = {"sample": torch.randn(8, 2048, 68, generator=g), "pred_xstart": torch.randn(8, 2048, 68, generator=g).double(),
+              "primitives": torch.randn(8, 2048, 3076, generator=g).half()}
+    rec = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    total = 0
+    for name, t in arrays.items():
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == (np.float64 if t.dtype == torch.float64 else np.float32) and rec[name]["shape"] == list(t.shape)
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "sample.npy"), arrays["sample"].numpy())
+    prim = np.load(tmp_path / "a" / "primitives.npy")
+    flat = arrays["primitives"].float().reshape(-1, 3076).numpy()
+    assert 0 < prim.shape[0] < flat.shape[0] and prim.shape[1] == 3076
+    rows = {r.tobytes() for r in flat}
+    assert all(r.tobytes() in rows for r in prim)                            # every stored row is a row of the array
+    assert total <= bench.DUMP_BUDGET_BYTES <= 64_000_000

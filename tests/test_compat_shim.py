@@ -96,17 +96,30 @@ def test_without_the_shim_the_reference_modules_are_used(fake_reference):
     assert r.returncode != 0 and "SHIM_OK" not in r.stdout
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="the reference checkout is only in the build container")
-def test_against_the_real_reference_layout():
-    """In the build container: the real checkout's packages, script dir first.  inference.py itself cannot be imported
-    here (omegaconf / rembg / nvdiffrast are absent), so the import lines that CAN resolve are executed."""
-    code = ("import sys; sys.path.insert(0, '/root/reference');"
+def test_against_the_real_reference_layout(tmp_path):
+    """The real checkout's package layout (tests/golden/reference_layout.json: every .py file of its models/, dva/ and utils/,
+    recorded by tests/golden/make_reference_layout.py) rebuilt from stub modules, script dir first: the shim's modules replace
+    exactly the hot-path names, every other module of the layout keeps importing from the checkout's tree."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_layout.json")) as f:
+        files = json.load(f)["files"]
+    replaced = {"models/dit_crossattn.py", "models/vae3d_dib.py", "models/attention.py", "models/primsdf.py",
+                "models/diffusion/__init__.py", "dva/ray_marcher.py"}
+    assert replaced <= set(files) and {"models/utils.py", "models/diffusion/respace.py", "dva/attr_dict.py"} <= set(files)
+    for rel in files:
+        f = tmp_path / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text("raise ImportError('the reference copy of this module must not be imported')\n" if rel in replaced
+                     else "WHO = 'reference'\n")
+    ref = str(tmp_path)
+    code = (f"import sys; sys.path.insert(0, {ref!r});"
             "from models.diffusion import create_diffusion; import models.utils, models.diffusion.respace;"
             "from dva.ray_marcher import RayMarcher; import dva.attr_dict;"
             "import importlib; import topia_xl_amd as p;"
             "assert importlib.import_module('models.dit_crossattn').DiT is p.DiT;"
             "assert importlib.import_module('models.vae3d_dib').VAE is p.VAE and create_diffusion is p.create_diffusion;"
-            "assert models.utils.__file__.startswith('/root/reference') and models.diffusion.respace.__file__.startswith('/root/reference');"
+            f"assert models.utils.__file__.startswith({ref!r}) and models.diffusion.respace.__file__.startswith({ref!r});"
+            "assert models.utils.WHO == models.diffusion.respace.WHO == dva.attr_dict.WHO == 'reference';"
             "print('REAL_OK')")
     r = _run([sys.executable, "-c", code], ROOT, {"PYTHONPATH": COMPAT})
     assert r.returncode == 0 and "REAL_OK" in r.stdout, r.stderr[-3000:]

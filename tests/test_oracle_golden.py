@@ -37,10 +37,23 @@ def test_schedule_tables_bit_exact(golden):
     assert abs(tab.acp[0] - 0.9999587158) < 1e-10 and abs(tab.acp[-1] - 3.689611e-3) < 1e-9
 
 
-def test_timestep_embedding(golden):
-    g = golden("dit_dh64")
-    mine = dit_ref.timestep_embedding(torch.tensor([0, 1, 40, 500, 960, 999]))
-    assert np.array_equal(mine.numpy(), g["t_emb_freq"])
+def test_timestep_embedding(golden, tmp_path):
+    """Bit-exact against the reference's embedding.  torch's CPU exp / cos / sin go through MKL's vector math, whose default code
+    path - and so the last bits - depends on the host CPU; the golden (tests/golden/t_emb.npz) was made with MKL_CBWR=COMPATIBLE,
+    the path MKL keeps identical on every x86 CPU, and the oracle runs in a child process in the same mode (MKL reads it at load)."""
+    import os
+    import subprocess
+    import sys
+    g = golden("t_emb")
+    assert str(g["mkl_cbwr"]) == "COMPATIBLE"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "mine.npy")
+    code = ("import sys, numpy as np, torch; from oracle import dit_ref; "
+            "np.save(sys.argv[1], dit_ref.timestep_embedding(torch.from_numpy(np.load(sys.argv[2])['t'])).numpy())")
+    r = subprocess.run([sys.executable, "-c", code, out, os.path.join(root, "tests", "golden", "t_emb.npz")], cwd=root,
+                       env={**os.environ, "MKL_CBWR": "COMPATIBLE"}, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert np.array_equal(np.load(out), g["t_emb_freq"])
 
 
 def _case(i):

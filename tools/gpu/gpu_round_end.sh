@@ -9,20 +9,20 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 if [ -z "$ONLY_PROFILES" ]; then
 timeout 1500 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider -s > $OUT/gpu_tests.log 2>&1; echo "pytest exit $?" >> $OUT/gpu_tests.log; tail -2 $OUT/gpu_tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu | tail -2 | tee $OUT/smoke.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?"; cut -c1-300 $OUT/bench_default.json
-timeout 600 python bench.py --config decode > $OUT/bench_decode.json 2> $OUT/bench_decode.err; echo "decode exit $?"
-timeout 900 python bench.py --config c4 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err; echo "c4 exit $?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench exit $?"; cut -c1-300 $OUT/bench_default.json
+timeout 600 python bench.py --full --config decode > $OUT/bench_decode.json 2> $OUT/bench_decode.err; echo "decode exit $?"
+timeout 900 python bench.py --full --config c4 --no-cpu-baseline > $OUT/bench_c4.json 2> $OUT/bench_c4.err; echo "c4 exit $?"
 : > $OUT/bench_other.jsonl
-timeout 600 python bench.py --batch 8 --steps 6 --warmup 2 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
-timeout 600 python bench.py --batch 8 --dtype bf16 --steps 6 --warmup 2 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
-timeout 600 python bench.py --batch 4 --n-prim 4096 --dtype bf16 --steps 6 --warmup 2 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
-timeout 600 python bench.py --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
+timeout 600 python bench.py --full --batch 8 --steps 6 --warmup 2 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
+timeout 600 python bench.py --full --batch 8 --dtype bf16 --steps 6 --warmup 2 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
+timeout 600 python bench.py --full --batch 4 --n-prim 4096 --dtype bf16 --steps 6 --warmup 2 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
+timeout 600 python bench.py --full --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-decode-leg >> $OUT/bench_other.jsonl 2>/dev/null
 fi   # (ONLY_PROFILES=1: the traces and counter passes alone)
 # the profiled commands carry --no-side-legs: the batch-8 / bf16 / torch-reference legs launch the same kernel names at other shapes
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- python bench.py --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs --steps 25 > $OUT/bench_trace.json 2> $OUT/bench_trace.err
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace_decode -- python bench.py --config decode --no-cpu-baseline --no-parity > $OUT/bench_trace_decode.json 2> $OUT/bench_trace_decode.err
-B="python bench.py --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs --steps 3 --warmup 1 --repeats 1 --no-kernel-events"
-D="python bench.py --config decode --no-cpu-baseline --no-parity --steps 2 --warmup 1 --repeats 1 --no-kernel-events"
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace -- python bench.py --full --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs --steps 25 > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace_decode -- python bench.py --full --config decode --no-cpu-baseline --no-parity > $OUT/bench_trace_decode.json 2> $OUT/bench_trace_decode.err
+B="python bench.py --full --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs --steps 3 --warmup 1 --repeats 1 --no-kernel-events"
+D="python bench.py --full --config decode --no-cpu-baseline --no-parity --steps 2 --warmup 1 --repeats 1 --no-kernel-events"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT -o fetch -- $B > /dev/null 2> $OUT/fetch.err
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT -o write -- $B > /dev/null 2> $OUT/write.err
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT -o fetch_decode -- $D > /dev/null 2> $OUT/fetch_decode.err
@@ -31,14 +31,14 @@ M="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIV
 timeout 300 rocprofv3 --kernel-trace --pmc $M --output-format csv -d $OUT -o mfma -- $B > /dev/null 2> $OUT/mfma.err
 timeout 300 rocprofv3 --kernel-trace --pmc $M --output-format csv -d $OUT -o mfma_decode -- $D > /dev/null 2> $OUT/mfma_decode.err
 # the batch-8 regime (T = 32768 token rows per launch: BASELINE configs[2] / [3] per GPU) - trace, traffic, matrix-pipe utilisation with the clock
-B8="python bench.py --batch 8 --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs"
+B8="python bench.py --full --batch 8 --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs"
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT -o trace_b8 -- $B8 --steps 6 --warmup 2 > $OUT/bench_trace_b8.json 2> $OUT/bench_trace_b8.err
 B8="$B8 --steps 2 --warmup 1 --repeats 1 --no-kernel-events"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT -o fetch_b8 -- $B8 > /dev/null 2> $OUT/fetch_b8.err
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT -o write_b8 -- $B8 > /dev/null 2> $OUT/write_b8.err
 timeout 300 rocprofv3 --kernel-trace --pmc $M --output-format csv -d $OUT -o mfma_b8 -- $B8 > /dev/null 2> $OUT/mfma_b8.err
 # configs[4] per GPU (bf16, N_prim = 4096, batch 4): the attention shape of VERDICT r5 item 6
-B4="python bench.py --batch 4 --n-prim 4096 --dtype bf16 --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs --steps 2 --warmup 1 --repeats 1 --no-kernel-events"
+B4="python bench.py --full --batch 4 --n-prim 4096 --dtype bf16 --no-cpu-baseline --no-parity --no-decode-leg --no-side-legs --steps 2 --warmup 1 --repeats 1 --no-kernel-events"
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT -o trace_c5 -- $B4 > /dev/null 2> $OUT/trace_c5.err
 timeout 300 rocprofv3 --kernel-trace --pmc $M --output-format csv -d $OUT -o mfma_c5 -- $B4 > /dev/null 2> $OUT/mfma_c5.err
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT -o fetch_c5 -- $B4 > /dev/null 2> $OUT/fetch_c5.err
