@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PRIMX_LIB") or os.path.join(_HERE, "csrc", "libprimx_
 F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF = 0, 1, 2
 HEADS_ROWS, HEADS_VT, HEADS_KROWS = 0, 1, 2
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -100,6 +100,10 @@ SIGNATURES = {
     "primx_attention_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(_l), C.POINTER(_l), C.POINTER(_l), _f, _p],
     "primx_layernorm_modulate_f32": [_p, _p, _p, _l, _p, _i, _i, _i, _f, _p],
     "primx_silu_f32": [_p, _p, _l, _p],
+    "primx_mcubes_workspace": [_i, _i, _i, C.POINTER(_l)],
+    "primx_mcubes_count": [_p, _i, _i, _i, _f, _p, _l, _p, _p],
+    "primx_mcubes_emit": [_p, _i, _i, _i, _f, _p, _l, _l, _l, _p, _p, _p, _p],
+    "primx_noise_filter": [_p, _i, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # an alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI: version 21 changed the
@@ -109,10 +113,12 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # version 24 added primx_dit_blocks_fold (one foreign call for a forward's blocks): a version-23 build lacks only that one, and the
 # host then issues the launches itself (`blocks_call_available()`); version 25 added primx_linear_heads_fold_pair and the kv_* tail of
 # PrimxDitForwardFold (a version-24 build ignores the tail: the host then projects K / V itself, `kv_ride_available()`); version 26 added
-# primx_linear_f32out_group (`f32out_group_available()`: without it the fold's u / v rows are one launch per site)
+# primx_linear_f32out_group (`f32out_group_available()`: without it the fold's u / v rows are one launch per site); version 27
+# added the mesh-extraction entry points (_MESH_ENTRY_POINTS: a version-26 build serves everything but mesh.py)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
-_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25)
+_MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
+_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26)
 _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
@@ -165,6 +171,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         if got < 25 and name == "primx_linear_heads_fold_pair":
             continue
         if got < 26 and name == "primx_linear_f32out_group":
+            continue
+        if got < 27 and name in _MESH_ENTRY_POINTS:
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes

@@ -109,6 +109,24 @@ def primsdf_from_denoised(path: str, device=None):
     return m.to(device).eval() if device is not None else m.eval()
 
 
+def primitives_to_mesh(recon_param_b: torch.Tensor, resolution: int = 256, **kw):
+    """recon_param[b] [N, 4 + 6 S^3] (srt = [:, :4], feat = [:, 4:]) -> `mesh.TriMesh`: a `PrimSDF` of the sample's
+    primitives (eval mode, on recon_param's device) through `mesh.extract_mesh(field, resolution, **kw)` - the GLB
+    export of inference.py:86-125 without the UV / texture bake."""
+    from .mesh import extract_mesh
+    from .primsdf import PrimSDF
+    if recon_param_b.dim() != 2:
+        raise ValueError(f"recon_param_b must be one sample [N, 4 + 6 S^3], got {tuple(recon_param_b.shape)}")
+    n, c = recon_param_b.shape
+    S = round(((c - 4) / 6) ** (1.0 / 3.0))
+    if 6 * S ** 3 != c - 4:
+        raise ValueError(f"recon_param_b has {c} channels, not 4 + 6 S^3")
+    m = PrimSDF(num_prims=n, dim_feat=6, prim_shape=S)
+    m.srt_param = torch.nn.Parameter(recon_param_b[:, :4].detach().float().contiguous(), requires_grad=False)
+    m.feat_param = torch.nn.Parameter(recon_param_b[:, 4:].detach().float().contiguous(), requires_grad=False)
+    return extract_mesh(m.eval(), resolution, **kw)
+
+
 def primitives_to_marcher_inputs(recon_param: torch.Tensor, volradius: float, sdf2alpha_var: float = 0.005):
     """recon_param [B, N, 4 + 6 S^3] -> (prim_rgba [B,N,4,S,S,S] in 0..255, prim_pos, prim_rot, prim_scale) exactly as the
     preview renderer prepares them (dva/visualize.py:215-239): alpha = 255 exp(-(sdf / 0.005)^2), rgb = 255 tex, identity

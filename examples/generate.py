@@ -2,10 +2,11 @@
 inference.py:312-352 does it:
 
   image -> DINOv2 tokens -> 25-step DDIM with CFG (DiT) -> de-normalise + VAE decode -> denoised.pt
-        -> PrimSDF lattice query (mesh-extraction input) + one ray-marched preview
+        -> PrimSDF lattice query (mesh-extraction input) + one ray-marched preview [+ GLB mesh with --mesh]
 
 There are no checkpoints offline: every network carries random weights, so the outputs are noise - the point is the
-data flow, the shapes and the per-stage timing.   python examples/generate.py [--steps 25] [--res 128] [--lattice 96]
+data flow, the shapes and the per-stage timing.
+    python examples/generate.py [--steps 25] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
 """
 import argparse
 import os
@@ -25,6 +26,8 @@ def main():
     ap.add_argument("--res", type=int, default=128, help="preview resolution")
     ap.add_argument("--lattice", type=int, default=96, help="SDF lattice resolution (the CLI uses 256)")
     ap.add_argument("--small", action="store_true", help="tiny networks (smoke run)")
+    ap.add_argument("--mesh", default=None, help="write the mesh of sample 0 as a GLB file here (off by default)")
+    ap.add_argument("--mesh-res", type=int, default=256, help="marching-cubes lattice resolution of --mesh (the CLI's 256)")
     a = ap.parse_args()
     __graft_entry__.build()
     import topia_xl_amd as pkg
@@ -91,6 +94,10 @@ def main():
     print("tokens", tuple(y.shape), "samples", tuple(samples.shape), "recon_param", tuple(recon.shape), "sdf grid",
           tuple(sdf.reshape(a.lattice, a.lattice, a.lattice).shape), "preview", tuple(view.shape),
           "coverage %.2f" % float((view[0, 3] > 0).float().mean()))
+    if a.mesh:
+        mesh = timed(f"mesh extraction, {a.mesh_res}^3 lattice", lambda: pipeline.primitives_to_mesh(recon[0], a.mesh_res))
+        mesh.write_glb(a.mesh)
+        print(f"mesh: {mesh.v.shape[0]} vertices, {mesh.f.shape[0]} triangles -> {a.mesh}")
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 26
+#define PRIMX_ABI_VERSION 27
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -487,6 +487,31 @@ int primx_latent_denorm(const float* x, const float* mean, const float* stdv, fl
  * fill of points no primitive covers (primsdf.py:78-100). */
 int primx_primsdf_query(const float* pts, const float* srt, const float* feat, const float* lin, float* out, int n, int P,
                         int S, int C, int eval_fill, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Mesh extraction (inference.py:86-125, extract_texmesh up to the texture bake).  ABI 27.
+ * -------------------------------------------------------------------------------------------- */
+
+/* Marching cubes over vol [nx, ny, nz] fp32 (linear index (i * ny + j) * nz + k, the meshgrid(indexing='ij') lattice of
+ * inference.py:108-116), replacing mcubes.marching_cubes(grid, iso) (inference.py:119).  A corner is inside when
+ * value < iso; the case table is generated by csrc/gen_mc_tables.py.  Two calls on one workspace:
+ *   primx_mcubes_count: classify every point + scan; totals [2] int64 (device) receives (vertices, triangles);
+ *   primx_mcubes_emit:  with those totals (read back by the caller), verts [V, 3] fp32 positions in index coordinates,
+ *                       normals [V, 3] fp32 unit lattice-gradient normals (NULL: not written), tris [F, 3] int32 wound
+ *                       from inside (lower values) to outside; V == F == 0 launches nothing.
+ * Vertices are ordered by (owner point, axis) - one per sign-changing lattice edge - and triangles by (cell, table
+ * order): the output is bitwise deterministic.  Needs nx, ny, nz >= 2 and 3 * nx * ny * nz < 2^31; the workspace
+ * (`ws`, `ws_bytes` >= primx_mcubes_workspace) is owned by the caller and must stay untouched between the two calls. */
+int primx_mcubes_workspace(int nx, int ny, int nz, int64_t* bytes);
+int primx_mcubes_count(const float* vol, int nx, int ny, int nz, float iso, void* ws, int64_t ws_bytes, int64_t* totals,
+                       void* stream);
+int primx_mcubes_emit(const float* vol, int nx, int ny, int nz, float iso, const void* ws, int64_t ws_bytes, int64_t nverts,
+                      int64_t ntris, float* verts, float* normals, int* tris, void* stream);
+
+/* Noise-primitive filter (inference.py:89-103): srt [P, 4] = (scale, x, y, z) -> keep [P] uint8, keep_i =
+ * min_j (||pos_i - pos_j|| + [i == j]) < scale_i + scale_argmin, first index on ties; bit-exact against the reference
+ * evaluated by torch on the CPU (distance summed as (dx^2 + dy^2) + dz^2, no FMA contraction). */
+int primx_noise_filter(const float* srt, int P, uint8_t* keep, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Primitive ray marcher, forward (dva/ray_marcher.py:142-229; dva/mvp/extensions/{utils,mvpraymarch})
