@@ -102,7 +102,8 @@ int primx_point_features(const float* x, int64_t row_stride, const float* freqs,
  * stream while a compute-bound kernel (attention, LayerNorm) runs, for the weights of the GEMM that follows.  No counterpart
  * in the reference (its weights are whatever the caches hold); results are unaffected.  ABI 19. */
 int primx_prefetch(const void* ptr, int64_t bytes, void* stream);
-/* out = cast16( silu(in) ) elementwise.  The SiLU in front of every adaLN Linear
+/* out = cast16( silu(in) ) elementwise, silu(in) = in / (1 + exp(-in)) evaluated in fp32 as torch evaluates it: -0 where exp(-in)
+ * overflows fp32 (in < -88.72), like the reference's nn.SiLU on its fp32 input.  The SiLU in front of every adaLN Linear
  * (models/dit_crossattn.py:40-43,69-72) producing the 16-bit GEMM operand. */
 int primx_silu_cast(const float* in, void* out, int dtype, int64_t n, void* stream);
 
