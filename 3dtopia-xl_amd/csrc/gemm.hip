@@ -2355,20 +2355,32 @@ extern "C" int primx_linear_gate_residual_fold(const void* A, const void* W, con
     return PRIMX_OK;
 }
 
+// The argument rules of a fold-consumer heads problem (primx_linear_heads_fold, problem 0 of primx_linear_heads_fold_pair): the layouts
+// first - segment count, shape, every segment's kind and destination - then the operand and fold pointers.  `what` prefixes the message.
+static int check_heads_fold_args(const char* name, const char* what, const void* A, const void* W, int M, int N, int K, int rows_per_batch,
+                                 int heads, int dh, int n_seg, const int* kind, void* const* dst, int n_pad, const float* part, const float* u,
+                                 const float* v, const float* center, const float* center_out) {
+    PRIMX_REQUIRE(kind && dst && n_seg >= 1 && n_seg <= 3, "%s: %sn_seg must be 1..3", name, what);
+    PRIMX_REQUIRE(heads > 0 && dh > 0 && N == n_seg * heads * dh && M > 0 && K > 0, "%s: %sN must equal n_seg*heads*dh", name, what);
+    PRIMX_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && n_pad >= rows_per_batch && n_pad % 16 == 0,
+                  "%s: %sneed M %% rows_per_batch == 0, n_pad >= rows_per_batch, n_pad %% 16 == 0", name, what);
+    for (int s = 0; s < n_seg; ++s) {
+        PRIMX_REQUIRE(kind[s] == PRIMX_HEADS_ROWS || kind[s] == PRIMX_HEADS_VT || kind[s] == PRIMX_HEADS_KROWS, "%s: %sbad kind", name, what);
+        PRIMX_REQUIRE(dst[s] != nullptr, "%s: %snull destination", name, what);
+    }
+    PRIMX_REQUIRE(A && W && part && u && v && center && center_out && center != center_out,
+                  "%s: %snull operand or fold argument, or center_out == center", name, what);
+    return PRIMX_OK;
+}
+
 extern "C" int primx_linear_heads_fold(const void* A, const void* W, int M, int N, int K, int rows_per_batch, int heads, int dh,
                                        int n_seg, const int* kind, void* const* dst, int n_pad, float scale0, const float* part,
                                        const float* u, const float* v, const float* center, float* center_out, float eps,
                                        int dtype, const void* prefetch, int64_t prefetch_bytes, void* stream) {
     const char* name = "primx_linear_heads_fold";
-    PRIMX_REQUIRE(kind && dst && n_seg >= 1 && n_seg <= 3, "%s: n_seg must be 1..3", name);
-    PRIMX_REQUIRE(heads > 0 && dh > 0 && N == n_seg * heads * dh, "%s: N must equal n_seg*heads*dh", name);
-    PRIMX_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && n_pad >= rows_per_batch && n_pad % 16 == 0,
-                  "%s: need M %% rows_per_batch == 0, n_pad >= rows_per_batch, n_pad %% 16 == 0", name);
-    PRIMX_REQUIRE(part && u && v && center && center_out && center != center_out, "%s: null fold argument, or center_out == center", name);
-    for (int s = 0; s < n_seg; ++s) {
-        PRIMX_REQUIRE(dst[s] != nullptr, "%s: null destination", name);
-        PRIMX_REQUIRE(kind[s] == PRIMX_HEADS_ROWS || kind[s] == PRIMX_HEADS_VT || kind[s] == PRIMX_HEADS_KROWS, "%s: bad kind", name);
-    }
+    if (int rc = check_heads_fold_args(name, "", A, W, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, part, u, v, center,
+                                       center_out))
+        return rc;
     PRIMX_DISPATCH_16(dtype, name, {
         using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
@@ -2417,11 +2429,9 @@ extern "C" int primx_linear_heads_fold_pair(const void* A, const void* W, int M,
                       "%s: problem 1: null destination or bad kind", name);
     bool paired = false;
     if (A) {
-        PRIMX_REQUIRE(W && kind && dst && n_seg >= 1 && n_seg <= 3 && heads > 0 && dh > 0 && N == n_seg * heads * dh && M > 0 && K > 0 &&
-                          rows_per_batch > 0 && M % rows_per_batch == 0 && n_pad >= rows_per_batch && n_pad % 16 == 0 && part && u && v &&
-                          center && center_out && center != center_out,
-                      "%s: problem 0: the argument rules of primx_linear_heads_fold", name);
-        for (int s = 0; s < n_seg; ++s) PRIMX_REQUIRE(dst[s] != nullptr, "%s: problem 0: null destination", name);
+        if (int rc = check_heads_fold_args(name, "problem 0: ", A, W, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, part, u, v,
+                                           center, center_out))
+            return rc;
     }
     PRIMX_DISPATCH_16(dtype, name, {
         using S = typename T16<DT>::S;

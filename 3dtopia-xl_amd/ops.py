@@ -360,23 +360,27 @@ def linear_f32out(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]
 def linear_f32out_group(problems: Sequence[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], torch.Tensor]], bias_from_row: int) -> bool:
     """primx_linear_f32out_group (ABI 26): every (A [M, K], W [N, K], bias [N] or None, out [M, N] fp32) of `problems` - same M, K and dtype -
     from ONE launch (the fold's u / v rows of a whole planned loop).  Returns False, having launched nothing, where the grouped kernel does
-    not apply (an older PRIMX_LIB build, PRIMX_UV_GROUP=0, N % 32 or K % 32 != 0): the caller then makes one linear_f32out call per problem."""
+    not apply (an older PRIMX_LIB build, PRIMX_UV_GROUP=0, N % 32 or K % 32 != 0, A or W not 16-byte aligned - the kernel reads them in
+    16-byte pieces - or operands on different devices): the caller then makes one linear_f32out call per problem."""
     if not problems or not _lib.f32out_group_available() or os.environ.get("PRIMX_UV_GROUP") == "0":
         return False
     M, K = problems[0][0].shape
     dt = problems[0][0].dtype
+    dev = problems[0][0].device
     rows, first = [], 0
     flops = 0.0
     for A, W, b, out in problems:
         N = W.shape[0]
         if (tuple(A.shape) != (M, K) or A.dtype != dt or W.shape[1] != K or tuple(out.shape) != (M, N) or N % 32 or K % 32
-                or not (A.is_contiguous() and W.is_contiguous() and out.is_contiguous()) or out.data_ptr() % 16):
+                or not (A.is_contiguous() and W.is_contiguous() and out.is_contiguous())
+                or (A.data_ptr() | W.data_ptr() | out.data_ptr()) % 16
+                or any(t.device != dev for t in (A, W, out) + ((b,) if b is not None else ()))):
             return False
         rows.append([_dev(A, "A"), _dev(W, "W", dt), _dev(b, "bias", dt) if b is not None else 0, _dev(out, "out", torch.float32),
                      N | (first << 32)])                          # (N, first_wg: two little-endian ints in the struct's last 8 bytes)
         first += (N + 127) // 128
         flops += 2.0 * M * N * K
-    table = torch.tensor(rows, dtype=torch.int64).to(problems[0][0].device, non_blocking=False)
+    table = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=False)
     _timed(f"None {len(problems)} problems x {M} rows, K = {K}", flops, lambda: check(_lib.load().primx_linear_f32out_group(
         table.data_ptr(), len(problems), first, M, K, bias_from_row, dtype_code(dt), _stream()), "primx_linear_f32out_group"))
     return True

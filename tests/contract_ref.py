@@ -283,7 +283,8 @@ def contract_report(got, exact_pre, ref, dtype, K, acc=None, ew_ulps=0.0, c=C_AC
     # 2. how many differ, against the allowance derived above
     rep["differ"] = int(np.sum(ok & (g != rf))) + rep["overflow_edge"]
     p_acc = np.minimum(1.0, (noise + np.broadcast_to(np.abs(_f64(extra)), _f64(exact_pre).shape).ravel()) / ulp16(a, dtype))
-    p_ew = np.minimum(1.0, 2.0 * ew_ulps * 2.0 ** -24 * np.abs(np.where(np.isfinite(pre), pre, 0.0)) / ulp16(pre, dtype))
+    ew = np.broadcast_to(_f64(ew_ulps), _f64(exact_pre).shape).ravel()
+    p_ew = np.minimum(1.0, 2.0 * ew * 2.0 ** -24 * np.abs(np.where(np.isfinite(pre), pre, 0.0)) / ulp16(pre, dtype))
     expect = float(np.sum(np.minimum(1.0, p_acc + p_ew)[fin]))
     rep["allowed"] = expect + 3.0 * math.sqrt(expect) + 3.0      # + counting noise of a sum of Bernoulli trials
     rep["differ_frac"] = rep["differ"] / max(1, n)
@@ -324,3 +325,224 @@ def gemm_abs_bound(A, W, bias=None, extra_terms=0) -> np.ndarray:
     n = Ad.shape[1] + 1 + extra_terms
     u = 2.0 ** -24
     return (n * u / (1 - n * u)) * s
+
+
+# ------------------------------------------------------------------------------------------------ the LayerNorm fold
+# include/primx_hip.h "The LayerNorm fold": with the row statistics mu, rho of the fp32 residual stream x, m = cast16(1 + scale),
+# a centre c and a scale rho_p per row,
+#     reference:  y = cast16( cast16( (x - mu) rho m + shift ) W^T + b )
+#     folded:     y = cast16( (rho / rho_p) a16 W^T - rho mu' u + v ),   a16 = cast16((x - c) rho_p m),  mu' = mean(x - c),
+#                 u = m W^T,  v = shift W^T + b  (fp32 rows)
+# The consumer's contract takes a16, the producer's partial sums `part`, the pairs `center` and the fp32 u, v AS GIVEN: the value in
+# front of its first rounding is the fold formula with float64 statistics of those partial sums and the exact a16 W^T.
+U32 = 2.0 ** -24
+GELU_LIPSCHITZ = 1.13      # max |d/dy gelu_tanh(y)| = 1.129 (at y = 1.5; the minimum is -0.13)
+
+
+def _rel_rsqrt_err(a):
+    """Largest relative change of 1 / sqrt(w) when w changes by a relative amount in [-a, a] (inf from a >= 1 on)."""
+    a = np.asarray(a, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(a < 1.0, np.maximum(1.0 / np.sqrt(np.maximum(1.0 - a, 1e-300)) - 1.0, 1.0 - 1.0 / np.sqrt(1.0 + a)), np.inf)
+
+
+def fold_partials_err(x, center, tile=144):
+    """Per-row bounds (d1, d2) of the PRODUCER's fp32 error in sum_k (x_k - c) and sum_k (x_k - c)^2 (over all column tiles), for
+    comparing `center_out` with the float64 statistics of x itself.  d = fl(x - c) is off by u |x - c|; a tile sums 144 terms in a
+    fixed order of depth < 144 (gamma_143 of the sum of magnitudes; d^2 adds one rounding and the square doubles d's):
+        d1 = gamma_145 sum_k |x_k - c|,   d2 = gamma_147 sum_k (x_k - c)^2,   gamma_n = n u / (1 - n u), u = 2^-24."""
+    xd = _f64(x)
+    c = _f64(center)[:, :1]
+    d = np.abs(xd - c)
+    g = lambda n: n * U32 / (1 - n * U32)
+    return g(tile + 1) * d.sum(-1), g(tile + 3) * (d * d).sum(-1)
+
+
+def fold_stats_ref(part, center, K, eps, part_err=None) -> dict:
+    """float64 statistics of a folded site from the partial sums `part` [M, P, 2] and the pairs `center` [M, 2] as given (the
+    consumer's input), and a bound on the CONSUMER's fp32 error in them (fold_stats_finish in csrc/gemm.hip).
+
+    Values: s1, s2 = the sums over the P partials; mu' = s1 / K, var = max(s2 / K - mu'^2, 0), rho = 1 / sqrt(var + eps),
+    center_out = (c + mu', rho).
+
+    Error bound (u = 2^-24, first order, x 1.01 for the second-order terms).  The kernel adds the P partials in order (gamma_{P-1}
+    of their magnitudes), multiplies by fl(1 / K) (two roundings), so
+        e_mu  = u ((P - 1) sum |s1_i| / K + 2 |mu'|).
+    E2 = s2 / K carries (P + 1) u E2 the same way; fl(mu^2) adds 2 |mu'| e_mu + u mu'^2; the difference one more u |var|:
+        e_var = u ((P + 1) E2 + mu'^2 + |var|) + 2 |mu'| e_mu  =  u ((P + 2) var + (P + 2) mu'^2) + ...,
+    i.e. relative to var a cancellation factor (1 + mu'^2 / var) - the price of var = E[(x - c)^2] - mu'^2 with a stale centre.
+    The clamp at 0 is 1-Lipschitz; + eps adds u (var + eps); sqrtf and the reciprocal are correctly rounded (no fast-math):
+        rel_rho = rsqrt_err((e_var + u (var + eps)) / (var + eps)) + 2 u       (rsqrt_err(a) ~ a / 2 for small a).
+    center_out[0] = fl(c + mu'_f): e_mu + u |c + mu'|;  center_out[1] = rho_f: rel_rho rho.
+    part_err = (d1, d2) per row (fold_partials_err): the producer's error in s1, s2 against x itself - then the bounds hold
+    against the float64 statistics of x (e_mu += d1 / K, e_var += d2 / K + 2 |mu'| d1 / K)."""
+    p = _f64(part)
+    cen = _f64(center)
+    P = p.shape[-2]
+    s1, s2 = p[..., 0].sum(-1), p[..., 1].sum(-1)
+    mu = s1 / K
+    e2 = s2 / K
+    raw = e2 - mu * mu
+    var = np.maximum(raw, 0.0)
+    epsf = f32(eps)
+    rho = 1.0 / np.sqrt(var + epsf)
+    e_mu = U32 * ((P - 1) * np.abs(p[..., 0]).sum(-1) / K + 2.0 * np.abs(mu))
+    e_var = U32 * ((P + 1) * np.abs(e2) + mu * mu + np.abs(raw)) + 2.0 * np.abs(mu) * e_mu
+    if part_err is not None:
+        d1, d2 = (_f64(t) for t in part_err)
+        e_mu = e_mu + d1 / K
+        e_var = e_var + d2 / K + 2.0 * np.abs(mu) * d1 / K
+    e_mu, e_var = 1.01 * e_mu, 1.01 * e_var
+    rel_rho = _rel_rsqrt_err((e_var + U32 * (var + epsf + e_var)) / (var + epsf)) + 2.0 * U32
+    c, rho_p = cen[:, 0], cen[:, 1]
+    center_out = np.stack([c + mu, rho], -1)
+    e_center = np.stack([e_mu + U32 * (np.abs(c + mu) + e_mu), rel_rho * rho], -1)
+    return dict(mu=mu, var=var, rho=rho, c=c, rho_p=rho_p, K=K, center_out=center_out, e_mu=e_mu, e_var=e_var, rel_rho=rel_rho,
+                e_center=e_center)
+
+
+def check_fold_center(got, stats, what="") -> float:
+    """center_out against fold_stats_ref: every pair within the derived fp32 bound.  Returns the largest fraction of it used."""
+    g = _f64(got)
+    assert np.all(np.isfinite(g)), f"{what}: center_out not finite"
+    err = np.abs(g - stats["center_out"])
+    frac = float(np.max(err / np.maximum(stats["e_center"], 1e-300)))
+    assert frac <= 1.0, f"{what}: center_out off by {frac:.3g} x its bound (row {int(np.argmax(np.max(err / stats['e_center'], -1)))})"
+    return frac
+
+
+def fold_value(acc, stats, u, v):
+    """The consumer's value in front of its first rounding: (rho / rho_p) acc - rho mu' u + v (float64; acc = exact a16 W^T)."""
+    g = (stats["rho"] / stats["rho_p"])[:, None]
+    return g * _f64(acc) - (stats["rho"] * stats["mu"])[:, None] * _f64(u)[None, :] + _f64(v)[None, :]
+
+
+def fold_consumer_ref(acc, stats, u, v, dtype, act=0, scale0=1.0):
+    """(pre, ref) of a fold consumer (primx_linear_heads_fold / primx_linear_fold): one rounding after the fold value; heads
+    segment 0 with scale0 != 1: a second rounding after the scale (primx_linear_heads: "multiplied by scale0 after rounding");
+    act: the activation between two roundings, as linear_ref."""
+    pre = fold_value(acc, stats, u, v)
+    y = r16(pre, dtype)
+    if f32(scale0) != 1.0:
+        pre = f32(scale0) * y
+        y = r16(pre, dtype)
+    if act:
+        pre = act64(y, act)
+        y = r16(pre, dtype)
+    return pre, y
+
+
+def fold_epilogue_err(y_minus_v, y, u, stats):
+    """Bound of the consumer epilogue's fp32 error in its value (beyond the accumulation's): with st0 = fl(rho_p mu'_f),
+    st1 = fl(rho_f / rho_p), t = fma(-st0, u, acc), y = fma(st1, t, v) and the statistics' errors of fold_stats_ref,
+        |y_f - y| <= (rel_rho + 2 u) |y - v| + rho (e_mu + u |mu'|) |u| + u |y|      (x 1.01)
+    because (rho / rho_p) |acc - rho_p mu' u| = |y - v|.  Arguments are magnitudes per element ([M, N]) / per column (u)."""
+    rr = (stats["rel_rho"] + 2.0 * U32)[:, None]
+    em = (stats["rho"] * (stats["e_mu"] + U32 * np.abs(stats["mu"])))[:, None]
+    return 1.01 * (rr * np.abs(_f64(y_minus_v)) + em * np.abs(_f64(u))[None, :] + U32 * np.abs(_f64(y)))
+
+
+def fold_contract_kw(acc, mag, stats, u, v, dtype, K, act=0, scale0=1.0, rms_axis=-1) -> dict:
+    """check_contract's arguments for a fold consumer.  acc = the exact a16 W^T, mag = its natural size per element
+    (max(sqrt(sum_k a_k^2 w_k^2), |acc|): the size of the partial sums the fp32 accumulation rounds).
+
+    check_contract models the accumulation noise from the rms over a row of the value in front of the first rounding, y0.  Here
+    the fp32 accumulation runs on a16 W^T and is scaled by the fold's gain rho / rho_p, and - mu' u cancels part of it, so the
+    noise is C_ACC sqrt(K) 2^-24 (rho / rho_p) mag: `gain` carries that ratio into criterion 1, `extra` the part of it above
+    check_contract's own noise into criterion 2.  The epilogue's fp32 error (fold_epilogue_err: the statistics, st0 / st1 and the
+    two fused multiply-adds) is an expected perturbation of y0 (`extra`) and widens criterion 1 (`inner`).  A second stage (the
+    scale0 of heads segment 0, the GELU) multiplies everything by |scale0| or GELU_LIPSCHITZ and lets y0's rounding flip by one
+    ulp16(y0) (`inner`), as in linear_ref's cases; the GELU's own fp32 error is derived below (`ew_ulps`).  rms_axis = 0 for outputs
+    checked column by column (check_contract on transposed arrays: the rms it bases its noise on is then a column's)."""
+    y0 = fold_value(acc, stats, u, v)
+    g = (stats["rho"] / stats["rho_p"])[:, None]
+    rms = np.sqrt(np.mean(np.where(np.isfinite(y0), y0, 0.0) ** 2, axis=rms_axis, keepdims=True))
+    scale = C_ACC * math.sqrt(K) * 2.0 ** -24
+    noise_c = scale * rms
+    noise_t = scale * g * _f64(mag)
+    E = fold_epilogue_err(y0 - _f64(v)[None, :], y0, u, stats)
+    staged = f32(scale0) != 1.0 or act != 0
+    sg = abs(f32(scale0)) if f32(scale0) != 1.0 else (GELU_LIPSCHITZ if act else 1.0)
+    gain = sg * noise_t / np.maximum(noise_c, 1e-300)
+    inner = sg * (E + (ulp16(y0, dtype) if staged else 0.0))
+    ew = 4.0 if staged else 0.0
+    if act == 1:
+        # GELU-tanh in fp32 is 0.5 y (1 + tanh(z)): tanh is good to a few ulps of 1, so the error is ABSOLUTE, about 0.5 |y| 4 u (+ the
+        # argument's 3 u |z| through tanh' = 1 - t^2, + 3 u |gelu| for the products) - many ulps of the result where 1 + tanh(z) cancels
+        # (y below -3), which the relative ew_ulps of linear_ref's cases does not cover.  In u32 units of |gelu(y)|:
+        yr = r16(y0, dtype)
+        z = math.sqrt(2.0 / math.pi) * (yr + 0.044715 * yr ** 3)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            ga = np.abs(gelu_tanh64(yr))
+            ew = np.where(ga > 0, (0.5 * np.abs(yr) * (4.0 + 3.0 * np.abs(z) * (1.0 - np.tanh(z) ** 2)) + 3.0 * ga) / ga, 4.0)
+        ew = np.where(np.isfinite(ew), ew, 1e30)
+    return dict(acc=y0, gain=gain, extra=np.maximum(noise_t - noise_c, 0.0) + E, inner=inner, ew_ulps=ew)
+
+
+def fold_site_bound(x, center, m, shift, W, b, a16, stats, u, v, dtype, act=0, scale0=1.0, eps=1e-6, mm=None):
+    """The folded output against the reference's UNFOLDED arithmetic, cast16(cast16(LN(x) m + shift) W^T + b) in float64 (LN with
+    the exact statistics of the fp32 rows x), and a per-element bound of their difference.  Returns (ref_out, bound).
+
+    From the header's identity, (rho / rho_p) a W^T - rho mu' u + v = rho (x - mu) m W^T + shift W^T + b for a = (x - c) rho_p m
+    exactly.  The two pre-rounding values differ by (u16 = 2^-p, the 16-bit unit roundoff; fp16 adds 2^-25 per subnormal term):
+      D1  the a16 rounding (and the three fp32 roundings in front of it): rho (u16 + 3 u) sum_k |x_k - c| |m_k| |w_k|;
+      D2  the reference's own rounding of the LayerNorm output: u16 sum_k |LN_k m_k + shift_k| |w_k|;
+      D3  the fp32 accumulation of a16 W^T (rigorous): (rho / rho_p) gamma_K sum_k |a16_k| |w_k|;
+      D4  the statistics (stats from fold_stats_ref WITH part_err: against x itself), st0 / st1 and the fused multiply-adds:
+          fold_epilogue_err with |y - v| <= |pre_ref - v| + D2;
+      D5  the fp32 rows u, v (gemm_abs_bound of [m; shift] W^T): rho |mu'| du + dv.
+    Both sides then round once (<= ulp16 apart beyond D); scale0 / GELU multiply by |scale0| / GELU_LIPSCHITZ and round again.
+    mm(A, B) = A @ B^T in float64 (numpy by default; the GPU tests pass a device matmul)."""
+    mm = mm or (lambda A_, B_: _f64(A_) @ _f64(B_).T)
+    xd = _f64(x)
+    c = _f64(center)[:, :1]
+    md, sd, Wd = _f64(m), _f64(shift), _f64(W)
+    bd = _f64(b) if b is not None else np.zeros(Wd.shape[0])
+    mu = xd.mean(-1, keepdims=True)
+    rho = 1.0 / np.sqrt(((xd - mu) ** 2).mean(-1, keepdims=True) + f32(eps))
+    lnm = (xd - mu) * rho * md[None, :] + sd[None, :]
+    pre_ref = mm(r16(lnm, dtype), Wd) + bd[None, :]
+    p, _, _ = _FMT[dtype]
+    u16 = 2.0 ** -p
+    sub = 2.0 ** -25 if dtype == torch.float16 else 0.0
+    aW = np.abs(Wd)
+    colsum = aW.sum(-1)[None, :]
+    g = (stats["rho"] / stats["rho_p"])[:, None]
+    d1 = rho * (u16 + 3 * U32) * mm(np.abs(xd - c) * np.abs(md)[None, :], aW) + g * sub * colsum
+    d2 = u16 * mm(np.abs(lnm), aW) + sub * colsum
+    K = Wd.shape[1]
+    d3 = g * (K * U32 / (1 - K * U32)) * mm(np.abs(_f64(a16)), aW)
+    v_ex = sd @ Wd.T + bd
+    u_ex = md @ Wd.T
+    du = gemm_abs_bound(md[None, :], Wd)[0]
+    dv = gemm_abs_bound(sd[None, :], Wd, b)[0]
+    d4 = fold_epilogue_err(np.abs(pre_ref - v_ex[None, :]) + d2, np.abs(pre_ref) + d1 + d2, np.abs(u_ex) + du, stats)
+    d5 = (stats["rho"] * np.abs(stats["mu"]))[:, None] * du[None, :] + dv[None, :]
+    D = d1 + d2 + d3 + d4 + d5
+    y_ref = r16(pre_ref, dtype)
+    _, _, fmax = _FMT[dtype]
+    with np.errstate(invalid="ignore", over="ignore"):
+        bound = D + ulp16(np.abs(pre_ref) + D, dtype)
+        edge = np.abs(np.abs(pre_ref) - (fmax + ulp16(fmax, dtype) / 2)) <= bound     # either side may overflow
+        out = y_ref
+        if f32(scale0) != 1.0:
+            s = abs(f32(scale0))
+            out = r16(f32(scale0) * y_ref, dtype)
+            bound = s * bound + ulp16(s * (np.abs(y_ref) + bound), dtype)
+        if act:
+            out = r16(act64(y_ref, act), dtype)
+            bound = GELU_LIPSCHITZ * bound + ulp16(np.abs(out) + GELU_LIPSCHITZ * bound, dtype) + 4 * U32 * np.abs(out)
+    return out, 1.01 * bound, edge
+
+
+def check_fold_site(got, ref_out, bound, edge, dtype, what="") -> float:
+    """Every element within the site bound of fold_site_bound, except where the unfolded value in front of the first rounding lies
+    within its bound of the overflow threshold (`edge`: either side may overflow there, and a GELU of -inf is NaN); elsewhere the
+    same inf / NaN on both sides.  Returns the largest fraction of the bound used."""
+    g, r = _f64(got), _f64(ref_out)
+    both = np.isfinite(g) & np.isfinite(r) & ~edge
+    frac = float(np.max(np.abs(g - r)[both] / bound[both])) if both.any() else 0.0
+    one = ~edge & ((np.isfinite(g) != np.isfinite(r)) | (np.isinf(g) & np.isinf(r) & (np.sign(g) != np.sign(r))))
+    assert not one.any(), f"{what}: {int(one.sum())} elements are inf / NaN on one side only, away from the overflow threshold"
+    assert frac <= 1.0, f"{what}: folded output off the unfolded reference by {frac:.3g} x the site bound"
+    return frac

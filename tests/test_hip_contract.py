@@ -53,7 +53,7 @@ def _kernel_family(name: str, dtype) -> str:
 
 # Every (kernel, epilogue) pair the default dispatch of csrc/gemm.hip can choose for primx_linear (EPI 0), _gate_residual[_ln] (1, 5),
 # _heads (2) and _residual (3), and the case below that reaches it (epilogue = the second template argument; the fold epilogues
-# have their own tests).  A pair added to the dispatch without a row here shows up as an unknown name in test_gemm_contract.
+# are in tests/test_hip_fold_contract.py).  A pair added to the dispatch without a row here shows up as an unknown name in test_gemm_contract.
 KERNELS = {
     "gemv16_kernel<.,4>": "linear M=3 (few-row GEMV)",
     "gemv16_kernel<.,8>": "linear M=7 (few-row GEMV)",

@@ -122,6 +122,28 @@ def test_linear_f32out_group(ops, dtype, M, frm):
     assert not ops.linear_f32out_group([(probs[0][0], probs[0][1][:40], None, torch.empty(M, 40, device=DEV))], frm)   # N % 32 != 0: the caller's loop
 
 
+def test_linear_f32out_group_rejects_misaligned_operands(ops):
+    """The grouped kernel reads A and W in 16-byte pieces: a contiguous view that starts 2 bytes into its storage is declined (False,
+    nothing launched, the output untouched) and the caller's per-problem loop takes it, as for operands on different devices."""
+    from topia_xl_amd import _lib
+    if not _lib.f32out_group_available() or os.environ.get("PRIMX_UV_GROUP") == "0":
+        pytest.skip("no grouped f32out kernel in this library / switched off")
+    M, N, K = 8, 128, 1152
+    A = synth.tensor(44, "A", (M, K)).to(torch.float16).to(DEV)
+    W = synth.tensor(44, "W", (N, K), K ** -0.5).to(torch.float16).to(DEV)
+    out = torch.full((M, N), float("nan"), device=DEV)
+    for bad_A, bad_W in ((True, False), (False, True)):
+        a = torch.empty(M * K + 1, dtype=A.dtype, device=DEV)[1:].view(M, K).copy_(A) if bad_A else A
+        w = torch.empty(N * K + 1, dtype=W.dtype, device=DEV)[1:].view(N, K).copy_(W) if bad_W else W
+        assert a.is_contiguous() and w.is_contiguous() and (a.data_ptr() % 16 != 0 or w.data_ptr() % 16 != 0)
+        assert not ops.linear_f32out_group([(a, w, None, out)], 0)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(out).all())
+    assert not ops.linear_f32out_group([(A, W.cpu(), None, out)], 0)                       # operands on two devices
+    assert ops.linear_f32out_group([(A, W, None, out)], 0)                                  # (the aligned problem runs)
+    assert rel_l2(out, A.double().cpu() @ W.double().cpu().t()) < 2e-6
+
+
 def _site(seed, B, n, D, K, dtype, mean_ratio=0.3, spread=2.0, offset=0.0, branch=1.0):
     """Inputs of one folded LayerNorm site: the branch operand A [B n, K] and weights of the PRODUCER (N = D), the residual
     stream x - row spread `spread`, a per-row mean of `mean_ratio` x the spread (+ `offset` with a per-row sign), gate (scaled
@@ -348,6 +370,11 @@ def test_fold_pair_rejects_bad_arguments(ops):
     bad0 = (16, 16, 4096, 3456, 1152, 2048, 16, 72, 3, None, None, 2048, 1.0, None, None, None, None, None, 1e-6)
     assert lib.primx_linear_heads_fold_pair(*bad0, 16, 16, None, 1536, 2304, 768, 1536, 16, 72, 2, k2, d2, 1536, 1.0, 1, None) == -1
     assert b"problem 0" in lib.primx_last_error()
+    # problem 0's layouts (its kinds included) are checked before its pointers: a bad kind is named even with the fold pointers NULL
+    k3, d3 = (C.c_int * 3)(0, 1, 7), (C.c_void_p * 3)(16, 16, 16)
+    bad_kind = (16, 16, 4096, 3456, 1152, 2048, 16, 72, 3, k3, d3, 2048, 1.0, None, None, None, None, None, 1e-6)
+    assert lib.primx_linear_heads_fold_pair(*bad_kind, 16, 16, None, 1536, 2304, 768, 1536, 16, 72, 2, k2, d2, 1536, 1.0, 1, None) == -1
+    assert b"problem 0: bad kind" in lib.primx_last_error(), lib.primx_last_error()
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
