@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PRIMX_LIB") or os.path.join(_HERE, "csrc", "libprimx_
 F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF = 0, 1, 2
 HEADS_ROWS, HEADS_VT, HEADS_KROWS = 0, 1, 2
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -104,6 +104,14 @@ SIGNATURES = {
     "primx_mcubes_count": [_p, _i, _i, _i, _f, _p, _l, _p, _p],
     "primx_mcubes_emit": [_p, _i, _i, _i, _f, _p, _l, _l, _l, _p, _p, _p, _p],
     "primx_noise_filter": [_p, _i, _p, _p],
+    "primx_texbake_labels": [_p, _p, _p, _i, _i, _p, _p],
+    "primx_texbake_components_workspace": [_i, _i, C.POINTER(_l)],
+    "primx_texbake_components": [_p, _i, _i, _p, _l, _p, C.POINTER(_l), _p],
+    "primx_texbake_raster_workspace": [_i, _i, C.POINTER(_l)],
+    "primx_texbake_raster": [_p, _p, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p],
+    "primx_texbake_compact": [_p, _i, _i, _p, _l, _p, _p, _i, _p, _p, _i, _i, _l, _p, _p, _p],
+    "primx_texbake_fill_workspace": [_i, _i, C.POINTER(_l)],
+    "primx_texbake_fill": [_p, _p, _l, _p, _i, _i, _i, _i, _p, _l, _p, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # an alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI: version 21 changed the
@@ -114,11 +122,15 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # host then issues the launches itself (`blocks_call_available()`); version 25 added primx_linear_heads_fold_pair and the kv_* tail of
 # PrimxDitForwardFold (a version-24 build ignores the tail: the host then projects K / V itself, `kv_ride_available()`); version 26 added
 # primx_linear_f32out_group (`f32out_group_available()`: without it the fold's u / v rows are one launch per site); version 27
-# added the mesh-extraction entry points (_MESH_ENTRY_POINTS: a version-26 build serves everything but mesh.py)
+# added the mesh-extraction entry points (_MESH_ENTRY_POINTS: a version-26 build serves everything but mesh.py); version 28 added
+# the texture-bake entry points (_TEXBAKE_ENTRY_POINTS: a version-27 build serves everything but mesh.py's texture bake)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
-_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26)
+_TEXBAKE_ENTRY_POINTS: set = {"primx_texbake_labels", "primx_texbake_components_workspace", "primx_texbake_components",
+                              "primx_texbake_raster_workspace", "primx_texbake_raster", "primx_texbake_compact",
+                              "primx_texbake_fill_workspace", "primx_texbake_fill"}
+_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27)
 _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
@@ -173,6 +185,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         if got < 26 and name == "primx_linear_f32out_group":
             continue
         if got < 27 and name in _MESH_ENTRY_POINTS:
+            continue
+        if got < 28 and name in _TEXBAKE_ENTRY_POINTS:
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes

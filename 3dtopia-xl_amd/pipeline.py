@@ -127,6 +127,24 @@ def primitives_to_mesh(recon_param_b: torch.Tensor, resolution: int = 256, **kw)
     return extract_mesh(m.eval(), resolution, **kw)
 
 
+def primitives_to_texmesh(recon_param_b: torch.Tensor, resolution: int = 256, texture_size: int = 1024, **kw):
+    """recon_param[b] [N, 4 + 6 S^3] -> `mesh.TexturedMesh`: the sample's primitives (as `primitives_to_mesh` builds them)
+    through `mesh.extract_texmesh(field, resolution, texture_size, **kw)` - the UV-mapped PBR GLB of inference.py:86-225
+    without `clean_mesh` / `decimate_mesh`."""
+    from .mesh import extract_texmesh
+    from .primsdf import PrimSDF
+    if recon_param_b.dim() != 2:
+        raise ValueError(f"recon_param_b must be one sample [N, 4 + 6 S^3], got {tuple(recon_param_b.shape)}")
+    n, c = recon_param_b.shape
+    S = round(((c - 4) / 6) ** (1.0 / 3.0))
+    if 6 * S ** 3 != c - 4:
+        raise ValueError(f"recon_param_b has {c} channels, not 4 + 6 S^3")
+    m = PrimSDF(num_prims=n, dim_feat=6, prim_shape=S)
+    m.srt_param = torch.nn.Parameter(recon_param_b[:, :4].detach().float().contiguous(), requires_grad=False)
+    m.feat_param = torch.nn.Parameter(recon_param_b[:, 4:].detach().float().contiguous(), requires_grad=False)
+    return extract_texmesh(m.eval(), resolution, texture_size, **kw)
+
+
 def primitives_to_marcher_inputs(recon_param: torch.Tensor, volradius: float, sdf2alpha_var: float = 0.005):
     """recon_param [B, N, 4 + 6 S^3] -> (prim_rgba [B,N,4,S,S,S] in 0..255, prim_pos, prim_rot, prim_scale) exactly as the
     preview renderer prepares them (dva/visualize.py:215-239): alpha = 255 exp(-(sdf / 0.005)^2), rgb = 255 tex, identity

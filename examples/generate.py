@@ -3,10 +3,12 @@ inference.py:312-352 does it:
 
   image -> DINOv2 tokens -> 25-step DDIM with CFG (DiT) -> de-normalise + VAE decode -> denoised.pt
         -> PrimSDF lattice query (mesh-extraction input) + one ray-marched preview [+ GLB mesh with --mesh]
+        [+ UV-mapped PBR GLB with --texmesh]
 
 There are no checkpoints offline: every network carries random weights, so the outputs are noise - the point is the
 data flow, the shapes and the per-stage timing.
     python examples/generate.py [--steps 25] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
+                                [--texmesh OUT.glb [--texture-size 1024]]
 """
 import argparse
 import os
@@ -28,6 +30,9 @@ def main():
     ap.add_argument("--small", action="store_true", help="tiny networks (smoke run)")
     ap.add_argument("--mesh", default=None, help="write the mesh of sample 0 as a GLB file here (off by default)")
     ap.add_argument("--mesh-res", type=int, default=256, help="marching-cubes lattice resolution of --mesh (the CLI's 256)")
+    ap.add_argument("--texmesh", default=None, help="write sample 0 as a UV-mapped PBR GLB (albedo + metallic-roughness "
+                    "textures) here; its lattice resolution is --mesh-res")
+    ap.add_argument("--texture-size", type=int, default=1024, help="texture edge of --texmesh (the reference's 1024)")
     a = ap.parse_args()
     __graft_entry__.build()
     import topia_xl_amd as pkg
@@ -98,6 +103,12 @@ def main():
         mesh = timed(f"mesh extraction, {a.mesh_res}^3 lattice", lambda: pipeline.primitives_to_mesh(recon[0], a.mesh_res))
         mesh.write_glb(a.mesh)
         print(f"mesh: {mesh.v.shape[0]} vertices, {mesh.f.shape[0]} triangles -> {a.mesh}")
+    if a.texmesh:
+        tm = timed(f"textured mesh, {a.mesh_res}^3 lattice, {a.texture_size}^2 textures",
+                   lambda: pipeline.primitives_to_texmesh(recon[0], a.mesh_res, a.texture_size))
+        tm.write_glb(a.texmesh)
+        print(f"textured mesh: {tm.v.shape[0]} vertices, {tm.f.shape[0]} triangles, "
+              f"{int(tm.covered.sum())} covered texels -> {a.texmesh}")
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 27
+#define PRIMX_ABI_VERSION 28
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -513,6 +513,58 @@ int primx_mcubes_emit(const float* vol, int nx, int ny, int nz, float iso, const
  * min_j (||pos_i - pos_j|| + [i == j]) < scale_i + scale_argmin, first index on ties; bit-exact against the reference
  * evaluated by torch on the CPU (distance summed as (dx^2 + dy^2) + dz^2, no FMA contraction). */
 int primx_noise_filter(const float* srt, int P, uint8_t* keep, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Texture bake (inference.py:126-211: UV unwrap, atlas raster, texel fill).  ABI 28.
+ * -------------------------------------------------------------------------------------------- */
+
+/* Face labels of the box-projection charts: v [V, 3] fp32, f [F, 3] int32, n [V, 3] fp32 vertex normals or NULL ->
+ * label [F] int32 in 0..5.  fp32 without FMA contraction:
+ *   1. g = (v1 - v0) x (v2 - v0); s = (n0 + n1) + n2, or g when n is NULL;
+ *   2. a = argmax |s| (ties to the lower axis), sign = that of s[a] (0 counts as +); if sign * g[a] <= 0.2f * |g|
+ *      (|g| = sqrt((gx^2 + gy^2) + gz^2)) the face is relabelled from g the same way; label = 2a + (sign < 0).
+ * Projection per label (u, v): +x (y, z), -x (z, y), +y (z, x), -y (x, z), +z (x, y), -z (y, x): every face with
+ * sign * g[a] > 0 has positive signed area in (u, v).  Needs 3F, 6V < 2^31; F == 0 launches nothing. */
+int primx_texbake_labels(const float* v, const float* n, const int* f, int V, int F, int* label, void* stream);
+
+/* Connected components of faces: faces whose corner nodes (node [F, 3] int32 in [0, U)) coincide are joined; for the
+ * charts node = vertex * 6 + label.  comp [F] int32 = rank of the component's smallest face index; *n_comp (host) =
+ * the number of components.  Union-find by root hooking (atomicMin onto the smaller id) + pointer jumping, a change flag
+ * read back every 4 rounds: SYNCHRONISES with the stream.  The workspace (ws_bytes >= primx_texbake_components_workspace)
+ * is owned by the caller.  F == 0 launches nothing and gives *n_comp = 0. */
+int primx_texbake_components_workspace(int F, int U, int64_t* bytes);
+int primx_texbake_components(const int* node, int F, int U, void* ws, int64_t ws_bytes, int* comp, int64_t* n_comp,
+                             void* stream);
+
+/* Atlas raster: uv [NUV, 2] int32 corner positions in 1/256 texel (texel (i, j) spans [256 j, 256 j + 256) x
+ * [256 i, 256 i + 256), its centre at (256 j + 128, 256 i + 128): uv = ((j + .5) / W, (i + .5) / H), row 0 = v 0), ft
+ * [F, 3] int32 corners of each face -> face_id [H, W] int32 (the smallest covering face, -1 = empty) and cover [H, W]
+ * int32 (how many faces cover the centre); totals [2] int64 (device) = (covered texels, texels covered more than once).
+ * Exact int64 edge functions: a centre is inside when every edge function is > 0, or == 0 on an edge (dx, dy) with
+ * dy < 0 or (dy == 0 and dx > 0) (the side a shift by (+eps, +eps^2) enters), so a centre on an edge or vertex shared
+ * by non-overlapping faces belongs to exactly one of them; faces with snapped area <= 0 cover nothing.  W, H in
+ * [1, 16384]; workspace (primx_texbake_raster_workspace) kept untouched until primx_texbake_compact. */
+int primx_texbake_raster_workspace(int W, int H, int64_t* bytes);
+int primx_texbake_raster(const int* uv, const int* ft, int NUV, int F, int W, int H, int* face_id, int* cover, void* ws,
+                         int64_t ws_bytes, int64_t* totals, void* stream);
+
+/* The n covered texels (n = totals[0] of primx_texbake_raster, read back by the caller) in raster order: texel [n]
+ * int32 = i * W + j and points [n, 3] fp32 = la v_a + lb v_b + lc v_c of the covering face's vertices (v [V, 3], f
+ * [F, 3]), la = fp32(E_bc) / fp32(area2) etc. from the integer edge functions at the centre, summed as (a + b) + c. */
+int primx_texbake_compact(const int* face_id, int W, int H, const void* ws, int64_t ws_bytes, const int* uv, const int* ft,
+                          int NUV, const float* v, const int* f, int V, int F, int64_t n, int* texel, float* points,
+                          void* stream);
+
+/* Quantize + fill (inference.py:186-211).  attr [n, 6] fp32 = the field query at the points of primx_texbake_compact
+ * (sdf, r, g, b, roughness, metallic); byte = trunc(fp32(x * 255)) (clamped to [0, 255]).  albedo [H, W, 3] = (r, g,
+ * b), metallic_roughness [H, W, 3] = (0, roughness, metallic).  The band = covered texels within city-block distance
+ * `band` of an uncovered texel or of a position outside the image; every uncovered texel within city-block distance
+ * `radius` of a covered one copies all channels of the band texel at the smallest squared Euclidean distance (ties: the
+ * smallest row, then column); other uncovered texels are 0.  radius in [1, 64], band in [1, 16]; workspace from
+ * primx_texbake_fill_workspace. */
+int primx_texbake_fill_workspace(int W, int H, int64_t* bytes);
+int primx_texbake_fill(const float* attr, const int* texel, int64_t n, const int* face_id, int W, int H, int radius,
+                       int band, void* ws, int64_t ws_bytes, uint8_t* albedo, uint8_t* metallic_roughness, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Primitive ray marcher, forward (dva/ray_marcher.py:142-229; dva/mvp/extensions/{utils,mvpraymarch})
