@@ -2,6 +2,9 @@
 // (models/primsdf.py:52-109, driven by inference.py:106-116 over 256^3 points and 180-193 over the visible texels).
 //
 //   w_i(x)   = relu(1 - ||(x - pos_i) / scale_i||_inf)                        (prim_weight, primsdf.py:103-107)
+//              = relu(1 - max_d |x_d - pos_d| / |scale_i|): a negative scale weighs as |scale| and samples at the signed
+//              (x - pos) / scale; a zero scale covers nothing here (the reference's weight is relu(1 - inf) = 0 there,
+//              except NaN at x == pos exactly)
 //   out(x)   = sum_i [w_i / (sum_j w_j + 1e-6)] * trilinear(feat_i, (x - pos_i) / scale_i)   (grid_sample_feat, 66-76;
 //              grid_sample 'bilinear', align_corners=True: x -> W (fastest), y -> H, z -> D of the [6, S, S, S] volume)
 //   eval mode, points no primitive covers: nearest primitive by ||x - pos||_2, nearest of its S^3 grid points,
@@ -46,8 +49,9 @@ __global__ __launch_bounds__(256) void primsdf_query_kernel(const float* __restr
                 if (d2 < best) { best = d2; best_i = p0 + t; }
             }
             const float m = fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz)));
-            if (!(m < q.x)) continue;                          // w = relu(1 - m / s) = 0
-            const float w = 1.0f - m / q.x;
+            const float as = fabsf(q.x);                       // ||(x - pos) / s||_inf = m / |s|: a negative scale covers
+            if (!(m < as)) continue;                           // w = relu(1 - m / |s|) = 0; s = 0 covers nothing
+            const float w = 1.0f - m / as;
             if (!(w > 0.f)) continue;
             wsum += w;
             // grid_sample, align_corners=True: index = (coord + 1) / 2 * (S - 1)

@@ -127,7 +127,6 @@ __global__ __launch_bounds__(256) void raymarch_kernel(const float* __restrict__
     const unsigned long long c_hit = stats ? __builtin_readcyclecounter() : 0;
     unsigned long long c_rebuild = 0, c_t0 = 0;
     // ---- march
-    const F3 ro = rp;                       // ray origin (t = 0) for the per-chunk interval tests
     int* sub = subs[wave];
     float t = tmin0;
     rp = {rp.x + rd.x * tmin0, rp.y + rd.y * tmin0, rp.z + rd.z * tmin0};
@@ -141,17 +140,20 @@ __global__ __launch_bounds__(256) void raymarch_kernel(const float* __restrict__
     // Every CHUNK steps the tile's hit list is filtered down to the primitives whose (per-ray) slab interval overlaps the
     // chunk for ANY ray of the wave, with a two-step safety margin; inside the chunk only those are transformed and
     // tested.  The filter is conservative, and a listed primitive the sample is not inside fails `in` exactly as before,
-    // so the image is the one the unfiltered loop produces.
+    // so the image is the one the unfiltered loop produces.  The intervals are measured from the sample position rp at
+    // the chunk start, not from ro + t rd: t and rp are accumulated separately in fp32 and drift apart by up to ~0.1 % of
+    // a step per step (t += 1e-4 in [2, 4) advances 419 ulps instead of 419.43) - tens of steps over a 2 x 10^4-step ray,
+    // far beyond the margin - while rp drifts from its own straight line by < 0.05 steps within one chunk.
     unsigned long long st_chunks = 0, st_nsub = 0, st_steps = 0, st_eval = 0;
     while (!__all(t > rtmax + 1e-5f || sat)) {
         if (stats) c_t0 = __builtin_readcyclecounter();
-        const float t_end = t + (float)CHUNK * stepsize;
+        const float c_end = (float)CHUNK * stepsize;     // chunk span, measured from the current sample position
         const bool live = !(t > rtmax + 1e-5f || sat);
         int nsub = 0;
         for (int ks = 0; ks < num; ++ks) {
             const int k = __builtin_amdgcn_readfirstlane(list[ks]);   // wave-uniform: the primitive record comes through scalar loads
             const float* pr = prot + k * 9;
-            const F3 xm = {ro.x - ppos[k * 3], ro.y - ppos[k * 3 + 1], ro.z - ppos[k * 3 + 2]};
+            const F3 xm = {rp.x - ppos[k * 3], rp.y - ppos[k * 3 + 1], rp.z - ppos[k * 3 + 2]};
             const float sx = pscl[k * 3], sy = pscl[k * 3 + 1], sz = pscl[k * 3 + 2];
             const F3 r0 = {(pr[0] * xm.x + pr[3] * xm.y + pr[6] * xm.z) * sx, (pr[1] * xm.x + pr[4] * xm.y + pr[7] * xm.z) * sy,
                            (pr[2] * xm.x + pr[5] * xm.y + pr[8] * xm.z) * sz};
@@ -161,16 +163,19 @@ __global__ __launch_bounds__(256) void raymarch_kernel(const float* __restrict__
             const float ax = (-1.f - r0.x) * ix, bx = (1.f - r0.x) * ix;
             const float ay = (-1.f - r0.y) * iy, by = (1.f - r0.y) * iy;
             const float az = (-1.f - r0.z) * iz, bz = (1.f - r0.z) * iz;
+            // the ray's interval inside primitive k, in t units from the current sample (step 0 of the chunk)
             const float trmin = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
             const float trmax = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-            // NaNs (ray parallel to a slab it touches) compare false everywhere: keep such a primitive
-            const bool skip = (trmax < t - 2.f * stepsize) || (trmin > t_end + 2.f * stepsize) || (trmin > trmax + 4.f * stepsize);
+            // NaNs compare false everywhere: keep such a primitive.  (A ray lying in a face plane gives one bound
+            // 0 * inf = NaN, but fminf / fmaxf drop it against the other bound's +-inf, so the interval stays ordered and
+            // empty - the ray is not strictly inside; only non-finite inputs reach the unordered case.)
+            const bool skip = (trmax < -2.f * stepsize) || (trmin > c_end + 2.f * stepsize) || (trmin > trmax + 4.f * stepsize);
             if (__any(live && !skip)) {
                 if (lane == 0) sub[nsub] = k;
                 if (nsub < NREC) {
                     // conservative step window of THIS ray inside primitive k during the chunk (two steps of margin each side;
                     // anything that does not compare cleanly - NaN, infinities - becomes "always")
-                    float e0 = floorf((trmin - t) / stepsize) - 2.f, e1 = ceilf((trmax - t) / stepsize) + 2.f;
+                    float e0 = floorf(trmin / stepsize) - 2.f, e1 = ceilf(trmax / stepsize) + 2.f;
                     unsigned short w = 0x00ff;                                   // first 255 > last 0: never
                     if (live && !skip) {
                         const int i0 = (e0 >= 0.f && e0 <= 255.f) ? (int)e0 : (e0 > 255.f ? 255 : 0);
