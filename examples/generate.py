@@ -8,7 +8,7 @@ inference.py:312-352 does it:
 There are no checkpoints offline: every network carries random weights, so the outputs are noise - the point is the
 data flow, the shapes and the per-stage timing.
     python examples/generate.py [--steps 25] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
-                                [--texmesh OUT.glb [--texture-size 1024]]
+                                [--texmesh OUT.glb [--texture-size 1024]] [--clean]
 """
 import argparse
 import os
@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--texmesh", default=None, help="write sample 0 as a UV-mapped PBR GLB (albedo + metallic-roughness "
                     "textures) here; its lattice resolution is --mesh-res")
     ap.add_argument("--texture-size", type=int, default=1024, help="texture edge of --texmesh (the reference's 1024)")
+    ap.add_argument("--clean", action="store_true", help="clean the --mesh / --texmesh mesh after marching cubes with "
+                    "inference.py:126's clean_mesh arguments (mesh.CLEAN_ARGS)")
     a = ap.parse_args()
     __graft_entry__.build()
     import topia_xl_amd as pkg
@@ -100,12 +102,13 @@ def main():
           tuple(sdf.reshape(a.lattice, a.lattice, a.lattice).shape), "preview", tuple(view.shape),
           "coverage %.2f" % float((view[0, 3] > 0).float().mean()))
     if a.mesh:
-        mesh = timed(f"mesh extraction, {a.mesh_res}^3 lattice", lambda: pipeline.primitives_to_mesh(recon[0], a.mesh_res))
+        mesh = timed(f"mesh extraction, {a.mesh_res}^3 lattice",
+                     lambda: pipeline.primitives_to_mesh(recon[0], a.mesh_res, clean=a.clean))
         mesh.write_glb(a.mesh)
         print(f"mesh: {mesh.v.shape[0]} vertices, {mesh.f.shape[0]} triangles -> {a.mesh}")
     if a.texmesh:
         tm = timed(f"textured mesh, {a.mesh_res}^3 lattice, {a.texture_size}^2 textures",
-                   lambda: pipeline.primitives_to_texmesh(recon[0], a.mesh_res, a.texture_size))
+                   lambda: pipeline.primitives_to_texmesh(recon[0], a.mesh_res, a.texture_size, clean=a.clean))
         tm.write_glb(a.texmesh)
         print(f"textured mesh: {tm.v.shape[0]} vertices, {tm.f.shape[0]} triangles, "
               f"{int(tm.covered.sum())} covered texels -> {a.texmesh}")

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 28
+#define PRIMX_ABI_VERSION 29
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -565,6 +565,69 @@ int primx_texbake_compact(const int* face_id, int W, int H, const void* ws, int6
 int primx_texbake_fill_workspace(int W, int H, int64_t* bytes);
 int primx_texbake_fill(const float* attr, const int* texel, int64_t n, const int* face_id, int W, int H, int radius,
                        int band, void* ws, int64_t ws_bytes, uint8_t* albedo, uint8_t* metallic_roughness, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Mesh cleanup (inference.py:126: clean_mesh(v, f, min_f=8, min_d=5, repair=True, remesh=False), the pymeshlab filters
+ * of utils/meshutils.py:118-193).  ABI 29.
+ * -------------------------------------------------------------------------------------------- */
+
+/* Rules.  Inputs v [V, 3] fp32, f [F, 3] int32 (indices in [0, V)); v_pct >= 0 and min_d >= 0 are percentages, min_f >= 0,
+ * repair.  fp32 steps have no FMA contraction; every sum is taken in the order written.
+ *   R0  Only vertices a face references take part (an unreferenced vertex is never a centre).
+ *   R1  D = the diagonal of the fp32 bounding box of the referenced vertices: extents in float64, D = sqrt((ex^2 + ey^2)
+ *       + ez^2) in float64.  r = fp32((v_pct / 100) * D), the product in float64.  v_pct == 0 skips R1-R2.
+ *   R2  Vertices in index order: vertex i is a centre iff no centre c < i lies within r of it; every other referenced
+ *       vertex joins the SMALLEST centre within r.  "Within": d2 = (dx dx + dy dy) + dz dz in fp32 (dx = x_i - x_j)
+ *       and d2 < fp32(r r), or d2 == 0.  Faces are remapped to centres; a face that then repeats a vertex is dropped.
+ *       Centres keep their positions.
+ *   R3  Faces with the same vertex set (any order) are duplicates: the lowest index is kept.
+ *   R4  g = (v1 - v0) x (v2 - v0) in fp32 (primx_texbake_labels' formula); g == (0, 0, 0) exactly: dropped.
+ *   R5  Faces sharing an edge (an unordered vertex pair) are joined into components.  A component is dropped when its
+ *       face count is < min_f, or its diagonal (as in R1, of its vertices) is < (min_d / 100) * D' in float64, D' = the
+ *       diagonal of the vertices referenced after R4.
+ *   R6  (repair) Candidates = the faces on an edge with more than 2 faces, ordered by (|g|, face index), |g| = sqrt((gx^2
+ *       + gy^2) + gz^2) in fp32.  In that order a candidate is dropped when one of its edges still has more than 2
+ *       undropped faces.
+ *   R7  (repair) Two faces at vertex x are in one fan when a chain of faces at x, each consecutive pair sharing an edge
+ *       (x, y), connects them.  A vertex with more than one fan gets ONE new vertex at its position, which takes the fan
+ *       of x's lowest-index incident face; new vertices are appended in order of (that face's index, corner).  A vertex
+ *       with three or more fans therefore stays non-manifold, as in the reference.
+ *   R8  Output: the vertices the surviving faces reference, in input order, then R7's new vertices; the surviving faces
+ *       in input order with remapped indices; vmap [V'] int64 = the input vertex of each output vertex (v' = v[vmap]
+ *       exactly).  Bitwise deterministic.
+ *
+ * Entry points, in call order; one workspace (ws_bytes >= primx_meshclean_workspace(V, F) of the input mesh) serves all
+ * of them and is owned by the caller.  Each ends in a host readback of the counts that size its outputs: SYNCHRONISES.
+ *   primx_meshclean_merge:      R0-R2 -> centre [V] int32 (the centre a referenced vertex joins, itself for a centre, -1
+ *                               when unreferenced); *rounds = the merge rounds that changed a state, *radius = r.  Grid:
+ *                               cells at least r wide, at most 128 per axis.
+ *   primx_meshclean_faces:      fr [F, 3] = centre[f], tid [F] in [0, F) = a dense id of each row's vertex set (equal
+ *                               sets, equal ids; rows that repeat a vertex are dropped whatever their id) -> the faces
+ *                               that survive R2-R4, in index order, in out_f [F, 3]; *n_out of them.
+ *   primx_meshclean_components: f [F, 3] (R4's survivors), node [F, 3] in [0, U) = a dense id per undirected edge (edge k
+ *                               = corners k, k + 1), comp [F] in [0, n_comp) = its edge-connected components
+ *                               (primx_texbake_components over node) -> R5's survivors in out_f / out_node [F, 3]; with
+ *                               repair the R6 candidates' keys cand_key [F] int64 = (bits of |g|) << 32 | the face's
+ *                               index in out_f, in face order.  counts (host) [3] = (faces kept, components removed,
+ *                               candidates).
+ *   primx_meshclean_edges:      f, node [F, 3] (R5's survivors), cand_key [n_cand] sorted ascending -> R6's survivors in
+ *                               out_f [F, 3]; *n_out of them.  The candidates are taken one after another on one lane.
+ *   primx_meshclean_fans:       f [F, 3] (the final faces), fan [3 F] int32 in [0, n_fans) = the fan of each corner
+ *                               (3 t + k; primx_texbake_components over nodes [e(x -> y), e(x -> z), e(x -> z)]), or
+ *                               NULL without repair -> out_f [F, 3] and vmap [<= 2 V] int64 of R8; counts (host) [2] =
+ *                               (referenced vertices, new vertices). */
+int primx_meshclean_workspace(int V, int F, int64_t* bytes);
+int primx_meshclean_merge(const float* v, const int* f, int V, int F, double v_pct, void* ws, int64_t ws_bytes, int* centre,
+                          int64_t* rounds, float* radius, void* stream);
+int primx_meshclean_faces(const float* v, const int* fr, const int* tid, int V, int F, void* ws, int64_t ws_bytes, int* out_f,
+                          int64_t* n_out, void* stream);
+int primx_meshclean_components(const float* v, const int* f, const int* node, const int* comp, int V, int F, int U,
+                               int n_comp, int min_f, double min_d, int repair, void* ws, int64_t ws_bytes, int* out_f,
+                               int* out_node, int64_t* cand_key, int64_t* counts, void* stream);
+int primx_meshclean_edges(const int* f, const int* node, int F, int U, const int64_t* cand_key, int64_t n_cand, void* ws,
+                          int64_t ws_bytes, int* out_f, int64_t* n_out, void* stream);
+int primx_meshclean_fans(const int* f, const int* fan, int V, int F, int n_fans, void* ws, int64_t ws_bytes, int* out_f,
+                         int64_t* vmap, int64_t* counts, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Primitive ray marcher, forward (dva/ray_marcher.py:142-229; dva/mvp/extensions/{utils,mvpraymarch})
