@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PRIMX_LIB") or os.path.join(_HERE, "csrc", "libprimx_
 F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF = 0, 1, 2
 HEADS_ROWS, HEADS_VT, HEADS_KROWS = 0, 1, 2
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
@@ -118,6 +118,14 @@ SIGNATURES = {
     "primx_meshclean_components": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _i, _p, _l, _p, _p, _p, C.POINTER(_l), _p],
     "primx_meshclean_edges": [_p, _p, _i, _i, _p, _l, _p, _l, _p, C.POINTER(_l), _p],
     "primx_meshclean_fans": [_p, _p, _i, _i, _i, _p, _l, _p, _p, C.POINTER(_l), _p],
+    "primx_meshdecim_workspace": [_i, _i, C.POINTER(_l)],
+    "primx_meshdecim_edges": [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p],
+    "primx_meshdecim_quadrics": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p],
+    "primx_meshdecim_costs": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p],
+    "primx_meshdecim_select": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p],
+    "primx_meshdecim_collapse": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _l, _p, C.POINTER(_l), _p],
+    "primx_meshdecim_finish": [_p, _p, _i, _i, _p, _l, _p, _p, _p, C.POINTER(_l), _p],
+    "primx_meshdecim_normals": [_p, _p, _p, _p, _i, _i, _p, _l, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # an alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI: version 21 changed the
@@ -130,7 +138,9 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # primx_linear_f32out_group (`f32out_group_available()`: without it the fold's u / v rows are one launch per site); version 27
 # added the mesh-extraction entry points (_MESH_ENTRY_POINTS: a version-26 build serves everything but mesh.py); version 28 added
 # the texture-bake entry points (_TEXBAKE_ENTRY_POINTS: a version-27 build serves everything but mesh.py's texture bake); version
-# 29 added the mesh-cleanup entry points (_MESHCLEAN_ENTRY_POINTS: a version-28 build serves everything but mesh.clean_mesh)
+# 29 added the mesh-cleanup entry points (_MESHCLEAN_ENTRY_POINTS: a version-28 build serves everything but mesh.clean_mesh);
+# version 30 added the mesh-decimation entry points (_MESHDECIM_ENTRY_POINTS: a version-29 build serves everything but
+# mesh.decimate_mesh)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
@@ -139,7 +149,10 @@ _TEXBAKE_ENTRY_POINTS: set = {"primx_texbake_labels", "primx_texbake_components_
                               "primx_texbake_fill_workspace", "primx_texbake_fill"}
 _MESHCLEAN_ENTRY_POINTS: set = {"primx_meshclean_workspace", "primx_meshclean_merge", "primx_meshclean_faces",
                                 "primx_meshclean_components", "primx_meshclean_edges", "primx_meshclean_fans"}
-_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28)
+_MESHDECIM_ENTRY_POINTS: set = {"primx_meshdecim_workspace", "primx_meshdecim_edges", "primx_meshdecim_quadrics",
+                                "primx_meshdecim_costs", "primx_meshdecim_select", "primx_meshdecim_collapse",
+                                "primx_meshdecim_finish", "primx_meshdecim_normals"}
+_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29)
 _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
@@ -198,6 +211,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         if got < 28 and name in _TEXBAKE_ENTRY_POINTS:
             continue
         if got < 29 and name in _MESHCLEAN_ENTRY_POINTS:
+            continue
+        if got < 30 and name in _MESHDECIM_ENTRY_POINTS:
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes

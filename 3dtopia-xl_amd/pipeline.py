@@ -112,7 +112,8 @@ def primsdf_from_denoised(path: str, device=None):
 def primitives_to_mesh(recon_param_b: torch.Tensor, resolution: int = 256, **kw):
     """recon_param[b] [N, 4 + 6 S^3] (srt = [:, :4], feat = [:, 4:]) -> `mesh.TriMesh`: a `PrimSDF` of the sample's
     primitives (eval mode, on recon_param's device) through `mesh.extract_mesh(field, resolution, **kw)` - the GLB
-    export of inference.py:86-125 without the UV / texture bake; `clean=True` adds the reference's `clean_mesh` step."""
+    export of inference.py:86-125 without the UV / texture bake; `clean=True` adds the reference's `clean_mesh` step and
+    `decimate=N` its `decimate_mesh` step (to at most N faces)."""
     from .mesh import extract_mesh
     from .primsdf import PrimSDF
     if recon_param_b.dim() != 2:
@@ -130,7 +131,8 @@ def primitives_to_mesh(recon_param_b: torch.Tensor, resolution: int = 256, **kw)
 def primitives_to_texmesh(recon_param_b: torch.Tensor, resolution: int = 256, texture_size: int = 1024, **kw):
     """recon_param[b] [N, 4 + 6 S^3] -> `mesh.TexturedMesh`: the sample's primitives (as `primitives_to_mesh` builds them)
     through `mesh.extract_texmesh(field, resolution, texture_size, **kw)` - the UV-mapped PBR GLB of inference.py:86-225
-    without `decimate_mesh`; `clean=True` adds the reference's `clean_mesh` step before the bake."""
+    `clean=True` adds the reference's `clean_mesh` step and `decimate=N` its `decimate_mesh` step (`mesh.DECIMATE_TARGET`
+    = 100000 in its configuration) before the bake."""
     from .mesh import extract_texmesh
     from .primsdf import PrimSDF
     if recon_param_b.dim() != 2:

@@ -8,7 +8,7 @@ inference.py:312-352 does it:
 There are no checkpoints offline: every network carries random weights, so the outputs are noise - the point is the
 data flow, the shapes and the per-stage timing.
     python examples/generate.py [--steps 25] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
-                                [--texmesh OUT.glb [--texture-size 1024]] [--clean]
+                                [--texmesh OUT.glb [--texture-size 1024]] [--clean] [--decimate N]
 """
 import argparse
 import os
@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--texture-size", type=int, default=1024, help="texture edge of --texmesh (the reference's 1024)")
     ap.add_argument("--clean", action="store_true", help="clean the --mesh / --texmesh mesh after marching cubes with "
                     "inference.py:126's clean_mesh arguments (mesh.CLEAN_ARGS)")
+    ap.add_argument("--decimate", type=int, default=0, help="then decimate the --mesh / --texmesh mesh to at most N faces "
+                    "when it has more (inference.py:128-129; the reference's value is 100000, mesh.DECIMATE_TARGET)")
     a = ap.parse_args()
     __graft_entry__.build()
     import topia_xl_amd as pkg
@@ -101,14 +103,27 @@ def main():
     print("tokens", tuple(y.shape), "samples", tuple(samples.shape), "recon_param", tuple(recon.shape), "sdf grid",
           tuple(sdf.reshape(a.lattice, a.lattice, a.lattice).shape), "preview", tuple(view.shape),
           "coverage %.2f" % float((view[0, 3] > 0).float().mean()))
+    dstats = {}
+
+    def report_decimation():
+        if dstats:
+            print("  of which mesh decimation: %d -> %d faces in %d rounds%s, %.1f ms" % (
+                dstats["faces_before"], dstats["faces_after"], dstats["rounds"], " (stalled)" if dstats["stalled"] else "",
+                1e3 * dstats["decimate_seconds"]))
+            dstats.clear()
+
     if a.mesh:
         mesh = timed(f"mesh extraction, {a.mesh_res}^3 lattice",
-                     lambda: pipeline.primitives_to_mesh(recon[0], a.mesh_res, clean=a.clean))
+                     lambda: pipeline.primitives_to_mesh(recon[0], a.mesh_res, clean=a.clean, decimate=a.decimate,
+                                                         stats=dstats))
+        report_decimation()
         mesh.write_glb(a.mesh)
         print(f"mesh: {mesh.v.shape[0]} vertices, {mesh.f.shape[0]} triangles -> {a.mesh}")
     if a.texmesh:
         tm = timed(f"textured mesh, {a.mesh_res}^3 lattice, {a.texture_size}^2 textures",
-                   lambda: pipeline.primitives_to_texmesh(recon[0], a.mesh_res, a.texture_size, clean=a.clean))
+                   lambda: pipeline.primitives_to_texmesh(recon[0], a.mesh_res, a.texture_size, clean=a.clean,
+                                                          decimate=a.decimate, stats=dstats))
+        report_decimation()
         tm.write_glb(a.texmesh)
         print(f"textured mesh: {tm.v.shape[0]} vertices, {tm.f.shape[0]} triangles, "
               f"{int(tm.covered.sum())} covered texels -> {a.texmesh}")

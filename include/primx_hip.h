@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 29
+#define PRIMX_ABI_VERSION 30
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -628,6 +628,93 @@ int primx_meshclean_edges(const int* f, const int* node, int F, int U, const int
                           int64_t ws_bytes, int* out_f, int64_t* n_out, void* stream);
 int primx_meshclean_fans(const int* f, const int* fan, int V, int F, int n_fans, void* ws, int64_t ws_bytes, int* out_f,
                          int64_t* vmap, int64_t* counts, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Mesh decimation (inference.py:128-129: decimate_mesh(v, f, 100000), pymeshlab's quadric edge collapse with
+ * optimalplacement=True, utils/meshutils.py:63-115).  ABI 30.
+ * -------------------------------------------------------------------------------------------- */
+
+/* Rules.  Inputs v [V, 3] fp32, f [F, 3] int32 (indices in [0, V)), target >= 0, optimalplacement.  Edges are collapsed
+ * in rounds; the edges of one round have pairwise disjoint neighbourhoods, so the result does not depend on the order in
+ * which they are taken.  Arithmetic is float64, IEEE + - x / only, no square root, no FMA contraction; (a b + c d) + e f
+ * is the order of every 3-term sum: dot(a, b) = (a0 b0 + a1 b1) + a2 b2, cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2,
+ * a0 b1 - a1 b0).
+ *   D0  State: positions p [V] = the fp32 input widened (float64 between rounds, rounded to fp32 once, on output), a
+ *       quadric Q [V] = (a00, a01, a02, a11, a12, a22, q0, q1, q2, c) of [[A, q], [q^T, c]], the live faces in input
+ *       order.  A face that repeats an index is not live.  Unreferenced vertices take no part.
+ *   D1  The quadric of a plane (n, d), d = -dot(n, point), has the coefficients (n_i n_j, n_i d, d d); with a weight w
+ *       each coefficient is (x y) w.  Face with corners p0, p1, p2: g = cross(p1 - p0, p2 - p0), plane (g, -dot(g, p0)),
+ *       no weight (the weight is (2 area)^2 by itself).  Edge k of a face (corners k -> k + 1 = a -> b) with exactly one
+ *       face: e = p_b - p_a, l2 = dot(e, e), m = cross(e, g), plane (m, -dot(m, p_a)), w = boundary_weight / l2 with
+ *       boundary_weight = 1, added to both endpoints (skipped when l2 == 0).  Q[x] = 0 + the contributions of x's corners
+ *       in ascending face order; within a face first the face's quadric, then those of its boundary edges at x in edge
+ *       order k = 0, 1, 2.  No floating-point atomics.
+ *   D2  Per round: the undirected edges of the live faces with dense ids in ascending (lo, hi) order (the sorted unique
+ *       keys lo V + hi), the faces per edge; a vertex is BOUNDARY on an edge with one face, LOCKED on an edge with more
+ *       than two.
+ *   D3  Edge (a, b), a < b: Q = Q[a] + Q[b] coefficient by coefficient.  Cofactors c00 = a11 a22 - a12 a12, c01 = a02 a12
+ *       - a01 a22, c02 = a01 a12 - a02 a11, c11 = a00 a22 - a02 a02, c12 = a01 a02 - a00 a12, c22 = a00 a11 - a01 a01;
+ *       det = (a00 c00 + a01 c01) + a02 c02; x_i = -((c_i0 q0 + c_i1 q1) + c_i2 q2) / det (c symmetric).  mid = (p_a + p_b)
+ *       0.5.  x is used iff optimalplacement, |det| > 1e-9 ((t t) t) with t = ((a00 + a11) + a22) / 3, and dot(x - mid,
+ *       x - mid) <= 4 dot(p_a - p_b, p_a - p_b) (no spikes).  Otherwise x = the cheapest of p_a, p_b, mid, a later one only
+ *       when strictly cheaper.  cost(y) = ((dot(y, A y) + 2 dot(q, y)) + c), (A y)_i = (a_i0 y0 + a_i1 y1) + a_i2 y2; a cost
+ *       that is not > 0 is 0.  key = (the upper 32 bits of the cost's float64 pattern) << 32 | edge id: unique, ordered as
+ *       the costs.
+ *   D4  Not valid: an endpoint is LOCKED; or the edge has two faces and both endpoints are BOUNDARY (a pinch); or the
+ *       edge has more than two faces.
+ *   D5  need = ceil((F - target) / 2).  Candidates = the valid edges among the min(E, 4 need) smallest keys.
+ *   D6  A candidate stays valid iff (flip) for every live face that holds exactly one of a, b, with n its g and n' its g
+ *       with that corner at x: dot(n, n') > 0; and (link) the vertices adjacent to both a and b number exactly the
+ *       edge's face count, and no edge is opposite a in one face without b and opposite b in another without a.
+ *   D7  m1[u] = the smallest key of a valid candidate at u; m2[u] = the smallest m1 over u and its neighbours; the
+ *       candidate is selected iff key == m2[a] == m2[b].  Two selected edges e, e' share no vertex (the shared vertex's
+ *       m2 would equal both keys) and have no adjacent endpoints (u of e next to u' of e': m2[u] <= m1[u'] <= key' and
+ *       m2[u'] <= key, so key == key'); faces of the two fans then have no common face, and every vertex a collapse reads
+ *       (the two fans' vertices) is moved by no other collapse.
+ *   D8  The selected edges in ascending key order; edge i is collapsed iff F - (the faces of the selected edges before
+ *       it) > target.
+ *   D9  Collapse: p[a] = x, Q[a] = Q[a] + Q[b], every b in a live face becomes a, faces that held both die.  Faces keep
+ *       their order and winding.
+ *   D10 Rounds repeat while F > target; a round without a collapse ends them (stalled: no valid candidate was left).
+ *       Output as R8: the referenced vertices in input order with positions fp32(p), the live faces re-indexed, vmap [V']
+ *       int64 = the input vertex each output vertex descends from (the surviving endpoint of its collapses).
+ * On an input whose edges all have one or two faces, wound consistently, the output has the same properties, the same
+ * Euler characteristic per component, the same components and boundary loops, no duplicate and no zero-area face, and
+ * F' is target or target - 1 unless stalled.
+ *
+ * Entry points, per round in call order (quadrics once, before the first round).  The caller owns every array; sorts and
+ * dense ids come from the caller: node [F, 3] = the dense id of edge k (corners k, k + 1), ukeys [U] int64 = the sorted
+ * unique lo V + hi, (sv, order) [3 F] = the corners' vertices sorted ascending and stably, and the corner (3 t + k) at
+ * each sorted position.  first / last [V] must be 0 for vertices no face references before the first call.
+ *   primx_meshdecim_edges:    D2 -> ecnt [U], vcls [V] (bit 0 BOUNDARY, bit 1 LOCKED), first / last [V] = each live
+ *                             vertex's range in (sv, order).
+ *   primx_meshdecim_quadrics: D0, D1 -> p [V, 3], Q [V, 10] float64.
+ *   primx_meshdecim_costs:    D3, D4 -> x [U, 3], cost [U], key [U] int64, valid [U].
+ *   primx_meshdecim_select:   cand [K] int64 = the K smallest keys ascending (D5) -> ok [K] (D4 and D6), sel [K] (D7);
+ *                             m1 [V] int64 is scratch.
+ *   primx_meshdecim_collapse: D8, D9 on p, Q, f in place -> the live faces in out_f [F, 3]; counts (host) [2] =
+ *                             (collapses, live faces).  SYNCHRONISES.  Workspace from primx_meshdecim_workspace(V, F).
+ *   primx_meshdecim_finish:   D10 -> out_v [<= V, 3] fp32, out_f [F, 3], vmap [<= V] int64, *n_out vertices.  SYNCHRONISES.
+ *   primx_meshdecim_normals:  normals [V, 3] fp32 = the float64 sum of g over each vertex's faces in ascending face
+ *                             order, divided by its length (0 when the sum is 0); not part of the bit-exact rules. */
+int primx_meshdecim_workspace(int V, int F, int64_t* bytes);
+int primx_meshdecim_edges(const int* f, const int* node, const int* sv, int V, int F, int U, int* ecnt, int* vcls,
+                          int* first, int* last, void* stream);
+int primx_meshdecim_quadrics(const float* v, const int* f, const int* node, const int* order, const int* first,
+                             const int* last, const int* ecnt, int V, int F, int U, double* p, double* Q, void* stream);
+int primx_meshdecim_costs(const double* p, const double* Q, const int64_t* ukeys, const int* ecnt, const int* vcls, int V,
+                          int U, int optimalplacement, double* x, double* cost, int64_t* key, int* valid, void* stream);
+int primx_meshdecim_select(const double* p, const int* f, const int* node, const int* order, const int* first,
+                           const int* last, const int64_t* ukeys, const int* ecnt, const int* valid, const double* x,
+                           const int64_t* cand, int V, int F, int U, int K, int64_t* m1, int* ok, int* sel, void* stream);
+int primx_meshdecim_collapse(double* p, double* Q, int* f, const int* order, const int* first, const int* last,
+                             const int64_t* ukeys, const int* ecnt, const double* x, const int64_t* cand, const int* sel,
+                             int V, int F, int U, int K, int target, void* ws, int64_t ws_bytes, int* out_f,
+                             int64_t* counts, void* stream);
+int primx_meshdecim_finish(const double* p, const int* f, int V, int F, void* ws, int64_t ws_bytes, float* out_v, int* out_f,
+                           int64_t* vmap, int64_t* n_out, void* stream);
+int primx_meshdecim_normals(const float* v, const int* f, const int* sv, const int* order, int V, int F, void* ws,
+                            int64_t ws_bytes, float* normals, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Primitive ray marcher, forward (dva/ray_marcher.py:142-229; dva/mvp/extensions/{utils,mvpraymarch})
