@@ -241,7 +241,7 @@ __global__ __launch_bounds__(THREADS) void noise_filter_kernel(const float* __re
         for (int t = 0; t < cnt; ++t) {
             const float4 q = s_prim[t];
             const float dx = me.y - q.y, dy = me.z - q.z, dz = me.w - q.w;
-            float dist = __fsqrt_rn((dx * dx + dy * dy) + dz * dz);   // sum(-1) of a 3-element row: (x + y) + z
+            float dist = sqrtf((dx * dx + dy * dy) + dz * dz);   // sum(-1) of a 3-element row: (x + y) + z; correctly rounded as torch.sqrt
             dist = dist + (j0 + t == i ? 1.f : 0.f);                  // dist += eye
             if (best_j < 0 || dist < best) { best = dist; best_j = j0 + t; }   // min(1): first index on ties
         }

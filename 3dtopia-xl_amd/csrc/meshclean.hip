@@ -408,7 +408,8 @@ __global__ __launch_bounds__(THREADS) void mc_cand_key_kernel(const float* __res
     int idx[3];
     float g[3] = {0.f, 0.f, 0.f};
     if (load_face(f, t, V, idx)) face_g(v, idx, g);
-    const float gn = __fsqrt_rn((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+    // sqrtf is the correctly rounded root; __fsqrt_rn compiles to the bare v_sqrt_f32 (1 ulp), which reorders near-ties of R6
+    const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
     cand_key[crank[t]] = ((long long)__float_as_int(gn) << 32) | (long long)frank[t];
 }
 

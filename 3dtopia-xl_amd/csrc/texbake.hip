@@ -78,7 +78,7 @@ __global__ __launch_bounds__(THREADS) void tb_labels_kernel(const float* __restr
     int lab = axis_label(s[0], s[1], s[2]);
     const int a = lab >> 1;
     const float ga = (lab & 1) ? -g[a] : g[a];
-    const float gn = __fsqrt_rn((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+    const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);   // correctly rounded (not __fsqrt_rn: v_sqrt_f32, 1 ulp)
     if (ga <= 0.2f * gn) lab = axis_label(g[0], g[1], g[2]);
     label[t] = lab;
 }

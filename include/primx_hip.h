@@ -522,7 +522,7 @@ int primx_noise_filter(const float* srt, int P, uint8_t* keep, void* stream);
  * label [F] int32 in 0..5.  fp32 without FMA contraction:
  *   1. g = (v1 - v0) x (v2 - v0); s = (n0 + n1) + n2, or g when n is NULL;
  *   2. a = argmax |s| (ties to the lower axis), sign = that of s[a] (0 counts as +); if sign * g[a] <= 0.2f * |g|
- *      (|g| = sqrt((gx^2 + gy^2) + gz^2)) the face is relabelled from g the same way; label = 2a + (sign < 0).
+ *      (|g| = sqrt((gx^2 + gy^2) + gz^2), the correctly rounded root) the face is relabelled from g the same way; label = 2a + (sign < 0).
  * Projection per label (u, v): +x (y, z), -x (z, y), +y (z, x), -y (x, z), +z (x, y), -z (y, x): every face with
  * sign * g[a] > 0 has positive signed area in (u, v).  Needs 3F, 6V < 2^31; F == 0 launches nothing. */
 int primx_texbake_labels(const float* v, const float* n, const int* f, int V, int F, int* label, void* stream);
@@ -586,7 +586,7 @@ int primx_texbake_fill(const float* attr, const int* texel, int64_t n, const int
  *       face count is < min_f, or its diagonal (as in R1, of its vertices) is < (min_d / 100) * D' in float64, D' = the
  *       diagonal of the vertices referenced after R4.
  *   R6  (repair) Candidates = the faces on an edge with more than 2 faces, ordered by (|g|, face index), |g| = sqrt((gx^2
- *       + gy^2) + gz^2) in fp32.  In that order a candidate is dropped when one of its edges still has more than 2
+ *       + gy^2) + gz^2) in fp32, the root correctly rounded.  In that order a candidate is dropped when one of its edges still has more than 2
  *       undropped faces.
  *   R7  (repair) Two faces at vertex x are in one fan when a chain of faces at x, each consecutive pair sharing an edge
  *       (x, y), connects them.  A vertex with more than one fan gets ONE new vertex at its position, which takes the fan

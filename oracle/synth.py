@@ -87,3 +87,41 @@ def state_dict_like(seed: int, reference_sd: Dict[str, torch.Tensor], gain: floa
             fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
             out[name] = tensor(seed, name, shape, (gain / max(fan_in, 1)) ** 0.5)
     return out
+
+
+def sphere_field(dev, P: int = 96, S: int = 8, noise: int = 0):
+    """Primitives on a sphere of radius 0.5 whose SDF payload is that sphere's distance function (seeded tensors for the
+    colour / material payload), plus `noise` isolated primitives at octant corners holding a small ball each.  The one
+    definition behind the mesh tests' synthetic field and the mesh benches' sphere (noise = 0)."""
+    from topia_xl_amd.primsdf import PrimSDF
+    gen = torch.Generator().manual_seed(23)
+    d = torch.randn(P, 3, generator=gen)
+    pos = 0.5 * d / d.norm(dim=1, keepdim=True)
+    scale = 0.16 + 0.04 * torch.rand(P, 1, generator=gen)
+    corners = [[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)][:noise]
+    far = torch.tensor(corners, dtype=torch.float32).reshape(-1, 3) * 0.85
+    pos = torch.cat([pos, far])
+    scale = torch.cat([scale, torch.full((noise, 1), 0.06)])
+    lin = torch.linspace(-1, 1, S)
+    Zg, Yg, Xg = torch.meshgrid(lin, lin, lin, indexing="ij")                 # [z][y][x] payload layout
+    local = torch.stack([Xg, Yg, Zg], -1).reshape(1, -1, 3)
+    pts = pos[:, None, :] + scale[:, None, :] * local
+    sdf = pts.norm(dim=-1) - 0.5
+    sdf[P:] = (pts[P:] - pos[P:, None, :]).norm(dim=-1) - 0.04               # noise primitives: a small ball each
+    rest = torch.rand(P + noise, 5 * S ** 3, generator=gen)
+    m = PrimSDF(num_prims=P + noise, prim_shape=S)
+    m.srt_param.data = torch.cat([scale, pos], 1)
+    m.feat_param.data = torch.cat([sdf, rest], 1)
+    return m.eval().to(dev)
+
+
+def sample_field(dev):
+    """A sample-like set of 2048 primitives posed the way examples/generate.py poses a random-weight sample (scale
+    0.05-0.08, centres in [-0.6, 0.6]^3, random payload)."""
+    from topia_xl_amd.primsdf import PrimSDF
+    gen = torch.Generator().manual_seed(42)
+    P, S = 2048, 8
+    m = PrimSDF(num_prims=P, prim_shape=S)
+    m.srt_param.data = torch.cat([0.05 + 0.03 * torch.rand(P, 1, generator=gen), 1.2 * torch.rand(P, 3, generator=gen) - 0.6], 1)
+    m.feat_param.data = torch.randn(P, 6 * S ** 3, generator=gen) * 0.5 + 0.3
+    return m.eval().to(dev)

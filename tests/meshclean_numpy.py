@@ -102,39 +102,57 @@ def merge_rounds(v, f, v_pct):
     """R0-R2 by the kernels' schedule -> (centre [V], rounds).  Every round reads the previous round's states: an
     undecided vertex becomes CAPTURED once a lower-index CENTRE lies within r, and is decided (CENTRE, or FINAL with
     its captor = the smallest such centre) once every lower-index vertex within r is decided.  `rounds` counts the
-    rounds that changed a state."""
+    rounds that changed a state.  A vertex's next state is a function of its own state and its lower neighbours', so a
+    round evaluates only the open vertices with a lower neighbour that changed in the round before (all of them in the
+    first round); every other vertex would get the state it has.  A large mesh then costs its pair list a few times over,
+    not once per round."""
     v = np.asarray(v, dtype=F32)
     f = np.asarray(f, dtype=np.int64)
-    centre = np.full(len(v), -1, dtype=np.int64)
+    V = len(v)
+    centre = np.full(V, -1, dtype=np.int64)
     ref = np.unique(f.reshape(-1))
     if v_pct == 0 or len(ref) == 0:
         centre[ref] = ref
         return centre, 0
     r = radius(v, f, v_pct)
     I, J = lower_pairs(v, ref, r)
-    st = np.full(len(v), UNDECIDED, dtype=np.int64)
+    o = np.argsort(I, kind="stable")                       # pairs grouped by the higher vertex ...
+    I, J = I[o], J[o]
+    cnt = np.bincount(I, minlength=V)
+    start = np.cumsum(cnt) - cnt
+    up = I[np.argsort(J, kind="stable")]                   # ... and every vertex's higher neighbours, grouped by it
+    ucnt = np.bincount(J, minlength=V)
+    ustart = np.cumsum(ucnt) - ucnt
+
+    def rows(lo, n):
+        return np.repeat(lo - (np.cumsum(n) - n), n) + np.arange(int(n.sum()))
+
+    st = np.full(V, UNDECIDED, dtype=np.int64)
     rounds = 0
     big = np.iinfo(np.int64).max
-    while True:
-        sj = st[J]
-        und = np.zeros(len(v), dtype=bool)
-        und[I[sj == UNDECIDED]] = True
-        mc = np.full(len(v), big, dtype=np.int64)
+    active = ref
+    while len(active):
+        k = rows(start[active], cnt[active])
+        i, j = I[k], J[k]
+        sj = st[j]
+        und = np.zeros(V, dtype=bool)
+        und[i[sj == UNDECIDED]] = True
+        mc = np.full(V, big, dtype=np.int64)
         m = sj == CENTRE
-        np.minimum.at(mc, I[m], J[m])
-        new = st.copy()
-        open_ = np.zeros(len(v), dtype=bool)
-        open_[ref] = True
-        open_ &= (st == UNDECIDED) | (st == CAPTURED)
-        done = open_ & ~und
-        new[done & (mc == big)] = CENTRE
-        new[done & (mc != big)] = FINAL
-        centre[done & (mc != big)] = mc[done & (mc != big)]
-        new[open_ & und & (mc != big) & (st == UNDECIDED)] = CAPTURED
-        if np.array_equal(new, st):
+        np.minimum.at(mc, i[m], j[m])
+        und, mc, old = und[active], mc[active], st[active]
+        new = old.copy()
+        new[~und & (mc == big)] = CENTRE
+        new[~und & (mc != big)] = FINAL
+        centre[active[~und & (mc != big)]] = mc[~und & (mc != big)]
+        new[und & (mc != big) & (old == UNDECIDED)] = CAPTURED
+        changed = active[new != old]
+        if len(changed) == 0:
             break
-        st = new
+        st[active] = new                                   # after every read of the round: the states are double-buffered
         rounds += 1
+        nxt = np.unique(up[rows(ustart[changed], ucnt[changed])])
+        active = nxt[(st[nxt] == UNDECIDED) | (st[nxt] == CAPTURED)]
     c = st == CENTRE
     centre[c] = np.nonzero(c)[0]
     return centre, rounds

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import primsdf_ref
+from oracle import primsdf_ref, synth
 from tests import mc_numpy
 from tests.test_mesh_cpu import parse_glb
 
@@ -139,28 +139,8 @@ def test_noise_filter_bit_exact(mesh):
 
 
 def _synthetic_field(P=96, S=8, noise=6):
-    """Primitives on a sphere of radius 0.5 whose SDF payload is that sphere's distance function (oracle.synth style
-    seeded tensors for the colour / material payload), plus a few isolated noise primitives."""
-    from topia_xl_amd.primsdf import PrimSDF
-    gen = torch.Generator().manual_seed(23)
-    d = torch.randn(P, 3, generator=gen)
-    pos = 0.5 * d / d.norm(dim=1, keepdim=True)
-    scale = 0.16 + 0.04 * torch.rand(P, 1, generator=gen)
-    far = torch.tensor([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)][:noise]) * 0.85   # octant corners
-    pos = torch.cat([pos, far])
-    scale = torch.cat([scale, torch.full((noise, 1), 0.06)])
-    lin = torch.linspace(-1, 1, S)
-    Zg, Yg, Xg = torch.meshgrid(lin, lin, lin, indexing="ij")                 # [z][y][x] payload layout
-    local = torch.stack([Xg, Yg, Zg], -1).reshape(1, -1, 3)
-    pts = pos[:, None, :] + scale[:, None, :] * local
-    sdf = pts.norm(dim=-1) - 0.5
-    sdf[P:] = (pts[P:] - pos[P:, None, :]).norm(dim=-1) - 0.04               # noise primitives: a small ball each
-    rest = torch.rand(P + noise, 5 * S ** 3, generator=gen)
-    feat = torch.cat([sdf, rest], 1)
-    m = PrimSDF(num_prims=P + noise, prim_shape=S)
-    m.srt_param.data = torch.cat([scale, pos], 1)
-    m.feat_param.data = feat
-    return m.eval().to(DEV)
+    """oracle.synth.sphere_field with a few isolated noise primitives, on the test device."""
+    return synth.sphere_field(DEV, P, S, noise)
 
 
 def test_extract_mesh(mesh, tmp_path):

@@ -19,32 +19,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import __graft_entry__  # noqa: E402
-
-
-def sphere_field(dev):
-    from topia_xl_amd.primsdf import PrimSDF
-    gen = torch.Generator().manual_seed(23)
-    P, S = 96, 8
-    d = torch.randn(P, 3, generator=gen)
-    pos = 0.5 * d / d.norm(dim=1, keepdim=True)
-    scale = 0.16 + 0.04 * torch.rand(P, 1, generator=gen)
-    lin = torch.linspace(-1, 1, S)
-    Zg, Yg, Xg = torch.meshgrid(lin, lin, lin, indexing="ij")
-    pts = pos[:, None, :] + scale[:, None, :] * torch.stack([Xg, Yg, Zg], -1).reshape(1, -1, 3)
-    m = PrimSDF(num_prims=P, prim_shape=S)
-    m.srt_param.data = torch.cat([scale, pos], 1)
-    m.feat_param.data = torch.cat([pts.norm(dim=-1) - 0.5, torch.rand(P, 5 * S ** 3, generator=gen)], 1)
-    return m.eval().to(dev)
-
-
-def sample_field(dev):
-    from topia_xl_amd.primsdf import PrimSDF
-    gen = torch.Generator().manual_seed(42)
-    P, S = 2048, 8
-    m = PrimSDF(num_prims=P, prim_shape=S)
-    m.srt_param.data = torch.cat([0.05 + 0.03 * torch.rand(P, 1, generator=gen), 1.2 * torch.rand(P, 3, generator=gen) - 0.6], 1)
-    m.feat_param.data = torch.randn(P, 6 * S ** 3, generator=gen) * 0.5 + 0.3
-    return m.eval().to(dev)
+from oracle.synth import sample_field, sphere_field  # noqa: E402,F401  (the mesh tests use the same two)
 
 
 def stage(name, fn, times):
