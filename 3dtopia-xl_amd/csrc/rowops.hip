@@ -463,6 +463,11 @@ extern "C" int primx_linear_f32(const float* in, const float* W, const float* bi
     PRIMX_REQUIRE(in && W && out, "primx_linear_f32: null pointer");
     PRIMX_REQUIRE(M > 0 && N > 0 && K > 0 && K % 4 == 0, "primx_linear_f32: need K%%4==0 (K=%d)", K);
     PRIMX_REQUIRE(!out2 || M > GEMV_MAX_ROWS, "primx_linear_f32: the second destination is for the tiled kernel (M > %d)", GEMV_MAX_ROWS);
+    // both kernels read `in` and W with 16-byte loads (rows are K % 4 == 0 floats apart); the tiled kernel stores 16 bytes
+    // per row segment when N % 4 == 0.  A contiguous view may start anywhere (t.flatten()[1:]...), so the bases are checked.
+    PRIMX_REQUIRE(((uintptr_t)in | (uintptr_t)W) % 16 == 0, "primx_linear_f32: in and W must be 16-byte aligned");
+    PRIMX_REQUIRE(M <= GEMV_MAX_ROWS || N % 4 != 0 || ((uintptr_t)out | (uintptr_t)out2) % 16 == 0,
+                  "primx_linear_f32: out / out2 must be 16-byte aligned when N %% 4 == 0");
     if (M <= GEMV_MAX_ROWS) {   // timestep-embedder MLP (M = B_e): stream the weight matrix once over the whole chip
         hipLaunchKernelGGL(gemv_f32_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, in, W, bias, out, M, N, K, act_out);
         PRIMX_CHECK_LAUNCH("primx_linear_f32");

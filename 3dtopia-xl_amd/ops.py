@@ -165,10 +165,10 @@ def point_features(x: torch.Tensor, freqs: torch.Tensor) -> torch.Tensor:
     """x: [T, C>=4] fp32 token rows (point = channels 1..3), freqs: [F] fp32 -> PointEmbed features [T, 6F+3], returned
     zero-padded to a multiple of 4 columns (the K granularity of primx_linear_f32)."""
     T, F = x.shape[0], freqs.shape[0]
-    if x.stride(1) != 1:
-        raise RuntimeError("point_features: channels must be contiguous")
+    if x.dim() != 2 or x.shape[1] < 4 or x.stride(1) != 1 or x.stride(0) < x.shape[1] or x.dtype != torch.float32 or not x.is_cuda:
+        raise RuntimeError("point_features: x must be fp32 [T, C >= 4] on a HIP device with contiguous channels (any row stride >= C)")
     out = torch.zeros(T, round_up(6 * F + 3, 4), dtype=torch.float32, device=x.device)
-    check(_lib.load().primx_point_features(_dev(x, "x", torch.float32), x.stride(0), _dev(freqs, "freqs", torch.float32),
+    check(_lib.load().primx_point_features(x.data_ptr(), x.stride(0), _dev(freqs, "freqs", torch.float32),
                                            out.data_ptr(), out.stride(0), T, F, _stream()), "primx_point_features")
     return out
 

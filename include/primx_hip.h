@@ -115,7 +115,10 @@ int primx_cast16(const float* in, void* out, int dtype, int64_t n, void* stream)
  * (out, in) layout, everything fp32 (these layers run outside autocast in the reference).
  * act_out: 0 none, 1 SiLU.  Used for x_embedder (models/dit_crossattn.py:141,191) and the
  * TimestepEmbedder MLP (models/utils.py:33-37).  `out2` (NULL or a second [M, N] buffer, M > 8): receives the same rows -
- * forward_with_cfg embeds cat([x, x]) (dit_crossattn.py:205), i.e. the same tokens into both halves of the residual stream. */
+ * forward_with_cfg embeds cat([x, x]) (dit_crossattn.py:205), i.e. the same tokens into both halves of the residual stream.
+ * K % 4 == 0; `in` and W 16-byte aligned, and out / out2 too when M > 8 and N % 4 == 0 (16-byte loads and stores): anything
+ * else is PRIMX_EINVAL before a launch.  SiLU is x / (1 + 2^(-x log2 e)) on the hardware exp2 (relative error about
+ * (2 |x| + 2) 2^-24 in the exponential); the sum is an fmaf chain in fp32. */
 int primx_linear_f32(const float* in, const float* W, const float* bias, float* out, float* out2, int M, int N, int K,
                      int act_out, void* stream);
 

@@ -546,3 +546,489 @@ def check_fold_site(got, ref_out, bound, edge, dtype, what="") -> float:
     assert not one.any(), f"{what}: {int(one.sum())} elements are inf / NaN on one side only, away from the overflow threshold"
     assert frac <= 1.0, f"{what}: folded output off the unfolded reference by {frac:.3g} x the site bound"
     return frac
+
+
+# ------------------------------------------------------------------------------------------------ 16-bit attention
+# attn_kernel / attn64_kernel are not one-rounding operations.  csrc/attention.hip documents what they approximate:
+#   dh = 72 (Q carries the mask / max columns): Q pre-scaled by c = scale log2(e) and rounded to 16 bits; the running max held
+#     as two 16-bit halves; P = exp2(s - m) packed round-toward-zero (fp16) / truncated (bf16) and used for BOTH the numerator
+#     and the denominator (the all-ones row of V^T);
+#   dh = 32 / 64 and the 64-token kernel: logits scaled in fp32; P rounded to nearest for the numerator, the denominator summed
+#     from the unrounded fp32 P;
+#   fp32 O and row sum, one reciprocal, one final rounding.
+# With w_j = softmax weights, out = sum_j w_j v_j, and relative weight errors eta_j, the output moves by
+#   sum_j w_j eta_j (v_j - out)   when numerator and denominator carry the same eta_j (a common factor cancels), and
+#   sum_j w_j eta_j v_j           when only the numerator does.
+# So, per element:  bound = 0.5 ulp16(out) + ln2 sum_j w_j |v_j - out| ds_j + dP sum_j w_j A_j + floor + fp32 terms, with
+#   ds_j = (u_q + (dh + 4) 2^-24) sum_d |q_d c k_jd| + 2^-22 max_j |s_j|   (exp2 units: Q's rounding u_q = 2^-11 / 2^-8 on the
+#          dh = 72 path, 0 else; fp32 accumulation of dh + 3 products and of c; the max's split and the exp2 argument),
+#   dP   = the pack's relative error (2^-10 / 2^-7 toward zero on the dh = 72 path, 2^-11 / 2^-8 to nearest else) + 2^-22 (v_exp),
+#   A_j  = |v_j - out| (same P in both sums) or |v_j| (numerator only),
+#   floor = 2^-24 sum_j A_j / L for fp16 (subnormal / flushed P below 2^-14 against the running max; L = sum_j 2^(s_j - max)),
+#   fp32 = gamma_nkv (sum_j w_j |v_j| + |out|) + 2^-22 |out|   (accumulation of O and of the row sum; the reciprocal and product).
+ATTN_SLACK = 2.0
+
+
+def attn_bound(q, k, v, scale, dtype, same_p):
+    """Exact output [B, Mq, H, dh] and the per-element bound above (float64 on q's device)."""
+    B, Mq, H, dh = q.shape
+    nkv = k.shape[1]
+    dev = q.device
+    c = f32(f32(scale) * 1.4426950408889634)
+    f16 = dtype == torch.float16
+    u_q = (2.0 ** -11 if f16 else 2.0 ** -8) if same_p else 0.0      # (same_p: the dh = 72 path)
+    dP = ((2.0 ** -10 if f16 else 2.0 ** -7) if same_p else (2.0 ** -11 if f16 else 2.0 ** -8)) + 2.0 ** -22
+    gam = nkv * 2.0 ** -24 / (1 - nkv * 2.0 ** -24)
+    outs, bounds = torch.empty(B, Mq, H, dh, dtype=torch.float64, device=dev), torch.empty(B, Mq, H, dh, dtype=torch.float64, device=dev)
+    for b in range(B):
+        for h in range(H):
+            Q, K, V = q[b, :, h].double(), k[b, :, h].double(), v[b, :, h].double()
+            S2 = (Q @ K.t()) * f32(scale) * 1.4426950408889634            # exact logits, exp2 units
+            m = S2.max(1, keepdim=True).values
+            Pm = torch.pow(2.0, S2 - m)
+            L = Pm.sum(1, keepdim=True)
+            w = Pm / L
+            out = w @ V
+            ds = (u_q + (dh + 4) * 2.0 ** -24) * ((Q.abs() @ K.abs().t()) * c) + 2.0 ** -22 * S2.abs().max(1, keepdim=True).values
+            D = (V[None] - out[:, None]).abs()                                 # [Mq, nkv, dh]
+            A = D if same_p else V.abs()[None].expand_as(D)
+            E = np.log(2.0) * torch.einsum("qj,qjd->qd", w * ds, D) + dP * torch.einsum("qj,qjd->qd", w, A)
+            if f16:
+                E = E + 2.0 ** -24 * A.sum(1) / L
+            E = E + gam * (w @ V.abs() + out.abs()) + 2.0 ** -22 * out.abs()
+            outs[b, :, h], bounds[b, :, h] = out, E
+            del D, A
+    return outs, bounds
+
+
+def attn_check(got, q, k, v, scale, dtype, same_p, what):
+    out, E = attn_bound(q, k, v, scale, dtype, same_p)
+    out_np = out.cpu().numpy()
+    bound = 0.5 * ulp16(out_np, dtype) + E.cpu().numpy()
+    g = _f64(got).reshape(out_np.shape)
+    err = np.abs(g - out_np)
+    ratio = float(np.max(err / bound))
+    print(f"attention {what} {dtype}: max |err| / bound = {ratio:.3f}")
+    assert ratio <= ATTN_SLACK, f"attention {what} {dtype}: error {ratio:.3f} x the derived bound"
+    # no bias: the mean signed error in ulps of the result, over the elements that do not cancel to near zero.  Asserted where
+    # every documented approximation is unbiased (P rounded to nearest).  The dh = 72 path packs P toward zero by design: a key
+    # at the running max keeps p = 1 exactly while every other key loses 2^-11 (fp16) / 2^-8 (bf16) of its weight on average,
+    # which pulls the output towards the dominant key's value - inside the bound above, but a bias; it is reported only.
+    rms = float(np.sqrt(np.mean(out_np ** 2)))
+    sel = np.abs(out_np) >= 0.25 * rms
+    bias = float(np.mean((g - out_np)[sel] * np.sign(out_np[sel]) / ulp16(out_np[sel], dtype)))
+    print(f"attention {what} {dtype}: mean signed error {bias:+.3f} ulp")
+    if not same_p:
+        assert abs(bias) <= BIAS_LIMIT, f"attention {what} {dtype}: biased by {bias:.3f} ulp"
+    return ratio
+
+
+# ------------------------------------------------------------------------------------------------ the fp32 entry points
+# csrc/fp32.hip (gemm_f32, attention_f32, layernorm_modulate_f32, silu_f32) and the fp32 front end of csrc/rowops.hip (linear_f32,
+# timestep_embedding, point_features, vit_tokens, row_stats) take fp32 and give fp32: nothing is rounded to 16 bits, so the contract
+# is "the float64 value, within what fp32 arithmetic in the documented order can lose".  Every helper below returns (exact, bound)
+# as float64 torch tensors on the device of its inputs (the shipped shapes are too large for the CPU inside a test); `bound` is a
+# worst-case bound per element from the standard model fl(a op b) = (a op b)(1 + d), |d| <= u = 2^-24, gamma_n = n u / (1 - n u)
+# for n accumulated roundings in ANY order (Higham, Accuracy and Stability of Numerical Algorithms, ch. 3), and the accuracy of
+# the device math functions in ulps.  No constant in them is measured.  They are asserted without a slack factor
+# (check_bound).  tests/test_fp32_contract_cpu.py proves on the CPU that numpy-fp32 restatements of the kernels' loops stay
+# inside them, and that the same restatements with one fault injected do not.
+#
+# Device math functions (ulps of the fp32 result).  The device library is built to the OpenCL C full-profile limits (OpenCL C
+# specification, "Relative error as ULPs": exp <= 3, tanh <= 5, erf <= 16, rsqrt <= 2); sinf / cosf are held to the 2 ulp this
+# project has promised for them since tests/test_hip_rowops.py::test_timestep_embedding_and_mlp (the specification's limit is 4).
+# v_exp_f32, the hardware exp2 behind __expf, is 1 ulp (CDNA3 / CDNA4 ISA guide).  Division and sqrtf are correctly rounded (hipcc's default
+# -fhip-fp32-correctly-rounded-divide-sqrt; the build sets no fast-math flag).
+EXP_ULPS, TANH_ULPS, ERF_ULPS, RSQRT_ULPS, SINCOS_ULPS = 3.0, 5.0, 16.0, 2.0, 2.0
+GELU_ERF_LIPSCHITZ = 1.13  # max |d/dy (y Phi(y))| = Phi(sqrt 2) + sqrt 2 phi(sqrt 2) = 1.129 (at y = sqrt 2)
+SILU_LIPSCHITZ = 1.10      # max |d/dy silu(y)| = 1.0998 (at y = 2.4)
+FLT_MAX = float.fromhex("0x1.fffffep127")
+
+
+def gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+def _t64(x) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        return x.detach().double()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+
+
+def ulp32(x: torch.Tensor) -> torch.Tensor:
+    """Spacing of fp32 at |x| (float64 tensor; the subnormal spacing 2^-149 below the normal range)."""
+    _, e = torch.frexp(torch.where(x == 0, torch.ones_like(x), x.abs()))        # |x| = m 2^e, m in [0.5, 1)
+    e = torch.where(x == 0, torch.full_like(e, -200), e)
+    return torch.ldexp(torch.ones_like(x), torch.clamp(e - 24, min=-149))
+
+
+def act64_t(y: torch.Tensor, act) -> torch.Tensor:
+    """0 identity, 1 tanh-GELU, 2 erf-GELU, "silu" (float64 torch)."""
+    if act == 1:
+        return 0.5 * y * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (y + 0.044715 * y ** 3)))
+    if act == 2:
+        return 0.5 * y * (1.0 + torch.special.erf(y / math.sqrt(2.0)))
+    if act == "silu":
+        return y * torch.sigmoid(y)
+    return y
+
+
+def act_eval_err(ya: torch.Tensor, act) -> torch.Tensor:
+    """Bound of the fp32 EVALUATION error of the activation at an argument of magnitude <= ya (non-decreasing in ya, so that it
+    can be taken at |y| + the argument's own bound).
+      tanh-GELU (gelu_tanh_exact, fp32.hip): z = c (x + 0.044715 x^3) carries 7 u |z| (the two rounded constants, four products,
+        one sum; |0.044715 x^3| <= |x + 0.044715 x^3|); T = tanhf(z): 7 u |z| (1 - T^2) + TANH_ULPS 2 u |T|, and |z| (1 - tanh^2 z)
+        <= 0.448; 1 + T one rounding of a value <= 2; 0.5 x is exact; the last product one rounding of |gelu| <= |x|:
+        0.5 |x| (7 (0.448) + 2 TANH_ULPS + 2) u + u |x| = (3.6 + TANH_ULPS) u |x|.  The error is ABSOLUTE in |x|: below y = -3 the sum
+        1 + T cancels and the result holds only a few of its own bits.
+      erf-GELU (gelu_erf_f): w = x / sqrt 2 carries 2 u |w|, through erf' = 2 / sqrt pi exp(-w^2): 2 u (0.484); erff ERF_ULPS 2 u;
+        1 + E and the product as above: 0.5 |x| (0.97 + 2 ERF_ULPS + 2) u + u |x| = (2.5 + ERF_ULPS) u |x|.
+      SiLU of primx_linear_f32 (silu_f, common.h: x / (1 + __expf(-x)), __expf(a) = v_exp_f32(a log2 e)): the rounded constant and
+        the product move the exp2 argument by 2 u |x| log2 e, the result by a relative 2 u |x|; v_exp_f32 2 u; so e = exp(-x) carries
+        (2 |x| + 2) u, the quotient |silu| (1 - sigma) (2 |x| + 2) u + 2 u |silu| (the sum and the division).  With x^2 sigma
+        (1 - sigma) <= 0.44 and |x| sigma (1 - sigma) <= 0.224: <= (1.4 + 2 |x|) u."""
+    if act == 1:
+        return (3.6 + TANH_ULPS) * U32 * ya
+    if act == 2:
+        return (2.5 + ERF_ULPS) * U32 * ya
+    if act == "silu":
+        return (1.4 + 2.0 * ya) * U32
+    return torch.zeros_like(ya)
+
+
+def gemm_f32_ref(A, W, bias=None, act=0, out_scale=1.0, gate_rows=None, x0=None):
+    """primx_gemm_f32 / primx_linear_f32 -> (exact, bound).
+
+    y = A W^T + bias is a chain of K fused multiply-adds and one addition in fp32: |y_f - y| <= gamma_(K+1) (sum |a||w| + |b|)
+    (gemm_abs_bound; any order, so it holds for the MFMA chain, the fmaf tiles and the wave-per-column kernel alike).
+      out = act(y) out_scale:  L |y_f - y| (L = the activation's Lipschitz constant) + act_eval_err(|y| + that bound), times
+                               |out_scale|, plus one rounding u |out| of the product;
+      gated, out = x0 + g y:   fl(x0 + fl(g y_f)) = two roundings (one if contracted): |g| gamma (1 + 2 u) + u (|x0| + 2 |g y|).
+    act: 0, 1 (tanh-GELU), 2 (erf-GELU) or "silu" (primx_linear_f32's act_out = 1).  gate_rows: the gate of each row [M, N]."""
+    Ad, Wd = _t64(A), _t64(W)
+    y = Ad @ Wd.t()
+    s = Ad.abs() @ Wd.abs().t()
+    if bias is not None:
+        y = y + _t64(bias)[None, :]
+        s = s + _t64(bias).abs()[None, :]
+    bnd = gamma(Ad.shape[1] + 1) * s
+    if gate_rows is not None:
+        g, x = _t64(gate_rows), _t64(x0)
+        return x + g * y, g.abs() * bnd * (1 + 2.0 ** -22) + 1.01 * U32 * (x.abs() + 2.0 * (g * y).abs())
+    L = {0: 1.0, 1: GELU_LIPSCHITZ, 2: GELU_ERF_LIPSCHITZ, "silu": SILU_LIPSCHITZ}[act]
+    E = L * bnd + act_eval_err(y.abs() + bnd, act)
+    sc = f32(out_scale)
+    out = sc * act64_t(y, act)
+    if sc != 1.0:
+        E = abs(sc) * E
+        E = E + U32 * (out.abs() + E)
+    return out, E
+
+
+def attn_f32_bound(q, k, v, scale, chunk=128):
+    """primx_attention_f32 -> (exact [B, Mq, H, dh], bound), float64 on q's device; q may hold a subset of the query rows.
+
+    attn_f32_kernel (fp32.hip): s_j = scale (q . k_j) by a chain of dh fused multiply-adds and one product; per 32-key tile the
+    running max m, p_j = __expf(s_j - m), the row sum l and O rescaled by alpha = __expf(m_old - m) and accumulated by fused
+    multiply-adds; out = O (1 / l).  No operand is rounded and the SAME p_j enters numerator and denominator, so with w_j the
+    softmax weights and relative errors eta_j of p_j the output moves by sum_j w_j eta_j (v_j - out): a common factor (every alpha,
+    the choice of m) cancels.  Natural-exp units, u = 2^-24:
+        ds_j  = (dh + 4) u sum_d |q_d k_jd| scale + 2 u max_j |s_j|     (the chain, the scale; slack for the max)
+        eta_j = ds_j + 4 u |s_j - m| + 4 u      (the subtraction u |s_j - m|; __expf's rounded log2 e and its product with the
+                                                 argument 2 u |s_j - m|; v_exp_f32 at 1 ulp = 2 u; one u of slack in each)
+        E     = sum_j w_j eta_j |v_j - out| + gamma_(nkv + tiles + 4) (sum_j w_j |v_j| + |out|) + 4 u |out|
+    (accumulation of O and of l over nkv keys and `tiles` rescales; the reciprocal and the last product)."""
+    B, Mq, H, dh = q.shape
+    nkv = k.shape[1]
+    sc = f32(scale)
+    gam = gamma(nkv + (nkv + 31) // 32 + 4)
+    outs = torch.empty(B, Mq, H, dh, dtype=torch.float64, device=q.device)
+    bounds = torch.empty_like(outs)
+    for b in range(B):
+        for h in range(H):
+            K, V = k[b, :, h].double(), v[b, :, h].double()
+            Ka, Va = K.abs(), V.abs()
+            for r0 in range(0, Mq, chunk):
+                Q = q[b, r0:r0 + chunk, h].double()
+                S = (Q @ K.t()) * sc
+                m = S.max(1, keepdim=True).values
+                P = torch.exp(S - m)
+                w = P / P.sum(1, keepdim=True)
+                out = w @ V
+                ds = (dh + 4) * U32 * ((Q.abs() @ Ka.t()) * abs(sc)) + 2.0 * U32 * S.abs().max(1, keepdim=True).values
+                eta = ds + 4.0 * U32 * (S - m).abs() + 4.0 * U32
+                D = (V[None] - out[:, None]).abs()                             # [chunk, nkv, dh]
+                E = torch.einsum("qj,qjd->qd", w * eta, D) + gam * (w @ Va + out.abs()) + 4.0 * U32 * out.abs()
+                outs[b, r0:r0 + chunk, h], bounds[b, r0:r0 + chunk, h] = out, E
+                del D
+    return outs, bounds
+
+
+def attn_f32_restate(q, k, v, scale, fault=None, fault_tile=-1):
+    """numpy-fp32 restatement of attn_f32_kernel's loop: q [G, Mq, dh], k, v [G, Nk, dh] (G = batch x heads) -> [G, Mq, dh] fp32.
+    32-key tiles, online max, fp32 exp, O and l rescaled per tile and O accumulated key by key in the kernel's order, one reciprocal.
+    (numpy's matmul stands for the short q . k chains.)
+    fault: None, or one injected bug for the teeth tests - "drop_last_key" (the last key of a ragged tile is masked),
+    "tail_zero" (the masked tail of a ragged tile scores 0 instead of -inf), "skip_rescale" (O is not rescaled in tile
+    `fault_tile`), "copy_row" (query row Mq - 1 lands in row Mq - 2 too)."""
+    q, k, v = (np.ascontiguousarray(t, dtype=np.float32) for t in (q, k, v))
+    G, Mq, dh = q.shape
+    Nk = k.shape[1]
+    sc = np.float32(scale)
+    m = np.full((G, Mq), -np.inf, np.float32)
+    l = np.zeros((G, Mq), np.float32)
+    O = np.zeros((G, Mq, dh), np.float32)
+    ntiles = (Nk + 31) // 32
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(ntiles):
+            k0, k1 = 32 * t, min(32 * t + 32, Nk)
+            ragged_last = k1 == Nk and Nk % 32 != 0
+            if fault == "drop_last_key" and ragged_last:
+                k1 -= 1
+                if k1 == k0:
+                    break
+            Kt, Vt = k[:, k0:k1], v[:, k0:k1]
+            S = np.matmul(q, Kt.transpose(0, 2, 1)) * sc
+            if fault == "tail_zero" and ragged_last:
+                pad = 32 - (k1 - k0)
+                S = np.concatenate([S, np.zeros((G, Mq, pad), np.float32)], -1)
+                Vt = np.concatenate([Vt, np.zeros((G, pad, dh), np.float32)], 1)
+            m_new = np.maximum(m, S.max(-1))
+            alpha = np.exp(m - m_new)
+            P = np.exp(S - m_new[..., None])
+            l = l * alpha + P.sum(-1, dtype=np.float32)
+            if not (fault == "skip_rescale" and t == fault_tile % ntiles):
+                O = O * alpha[..., None]
+            for j in range(Vt.shape[1]):                    # key by key, as the kernel's chain of multiply-adds (two roundings here)
+                O = O + P[..., j:j + 1] * Vt[:, None, j, :]
+            m = m_new
+    out = O * (np.float32(1.0) / l)[..., None]
+    if fault == "copy_row" and Mq >= 2:
+        out[:, Mq - 2] = out[:, Mq - 1]
+    return out
+
+
+def ln_stats_bound(x, eps, n_mean, n_var, rstd_u):
+    """Two-pass LayerNorm statistics of fp32 rows in fp32 -> dict(mu, var, rstd, e_mu, rel_r) (float64, [rows, 1]).
+
+    mean_f = fl(sum x / D) with n_mean roundings in any order: e_mu = gamma_(n_mean) mean |x|.  With d = mu - mean_f (one value per
+    row) the centred values are c_i^ = (c_i + d)(1 + t_i), |t_i| <= u, c_i = x_i - mu, and because sum_i c_i = 0
+        sum_i (c_i + d)^2 / D = var + d^2   EXACTLY  (the first-order term 2 d sum c_i vanishes: a wrong mean costs its square),
+    so the computed variance is off by  e_var = e_mu^2 + (2.01 u + gamma_(n_var)) (var + e_mu^2): the roundings t_i, and the n_var
+    roundings of the squares, their sum and the division (all terms non-negative, so the sum's error is relative).  Adding eps is
+    one more rounding; rstd carries rstd_u (the device function's error, relative, in units of u):
+        rel_r = rsqrt_err((e_var + u (var + eps + e_var)) / (var + eps)) + rstd_u u."""
+    xd = _t64(x)
+    D = xd.shape[-1]
+    mu = xd.mean(-1, keepdim=True)
+    var = ((xd - mu) ** 2).mean(-1, keepdim=True)
+    e_mu = gamma(n_mean) * xd.abs().mean(-1, keepdim=True)
+    e_var = e_mu ** 2 + (2.01 * U32 + gamma(n_var)) * (var + e_mu ** 2)
+    epsf = f32(eps)
+    a = (e_var + U32 * (var + epsf + e_var)) / (var + epsf)
+    rel_r = torch.where(a < 1.0, torch.maximum(1.0 / torch.sqrt(torch.clamp(1.0 - a, min=1e-300)) - 1.0, 1.0 - 1.0 / torch.sqrt(1.0 + a)),
+                        torch.full_like(a, float("inf"))) + rstd_u * U32
+    return dict(mu=mu, var=var, rstd=1.0 / torch.sqrt(var + epsf), e_mu=e_mu, rel_r=rel_r, D=D)
+
+
+def layernorm_modulate_f32_ref(x, shift_rows, scale_rows, eps=1e-6):
+    """primx_layernorm_modulate_f32 -> (exact, bound): (x - mu) rstd (1 + scale) + shift, shift_rows / scale_rows = the
+    modulation row of each x row ([rows, D]).
+
+    ln_modulate_f32_kernel: mean = fl(sum / D) (D + 1 roundings with the division's slack), var likewise over the squares
+    (n_var = D + 2), rstd = rsqrtf (RSQRT_ULPS ulp = 2 RSQRT_ULPS u).  Then per element c^ = fl(x - mean_f), off by
+    e_c = e_mu + u (|c| + e_mu); P = fl(fl(c^ rstd_f) fl(1 + scale)): three roundings; out = fl(P + shift):
+        |P_f - P| <= rstd |1 + scale| (e_c + (|c| + e_c) (rel_r + 3 u)),    bound = that + u (|P| + |shift| + that),   x 1.01 for
+    the products of small terms."""
+    st = ln_stats_bound(x, eps, x.shape[-1] + 1, x.shape[-1] + 2, 2.0 * RSQRT_ULPS)
+    xd, sh, sc = _t64(x), _t64(shift_rows), _t64(scale_rows)
+    c = xd - st["mu"]
+    P = c * st["rstd"] * (1.0 + sc)
+    e_c = st["e_mu"] + U32 * (c.abs() + st["e_mu"])
+    eP = st["rstd"] * (1.0 + sc).abs() * (e_c + (c.abs() + e_c) * (st["rel_r"] + 3.0 * U32))
+    return P + sh, 1.01 * (eP + U32 * (P.abs() + sh.abs() + eP))
+
+
+def ln_f32_restate(x, shift_rows, scale_rows, eps=1e-6, pad_mean=False):
+    """numpy-fp32 restatement of ln_modulate_f32_kernel (two-pass statistics, rsqrt as 1 / sqrt in fp32, the epilogue's operation
+    order).  pad_mean: the injected fault "mean over the padded length 64 ceil(D / 64)"."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    D = x.shape[-1]
+    n = np.float32(64 * ((D + 63) // 64) if pad_mean else D)
+    mean = x.sum(-1, keepdims=True, dtype=np.float32) / n
+    c = x - mean
+    var = (c * c).sum(-1, keepdims=True, dtype=np.float32) / np.float32(D)
+    rstd = np.float32(1.0) / np.sqrt(var + np.float32(eps))
+    return c * rstd * (np.float32(1.0) + np.asarray(scale_rows, np.float32)) + np.asarray(shift_rows, np.float32)
+
+
+def row_stats_ref(x, eps):
+    """primx_row_stats -> (exact [rows, 2], bound [rows, 2]) for the pairs (mean, rstd).
+
+    row_stats_kernel (the summation order of ln_row.h: four columns per lane and 128-column step, a 5-step half-wave tree; any
+    order is covered): mean = fl(sum fl(1 / D)): D + 2 roundings; var = fl(sum of squares fl(1 / D)): D + 3; rstd = 1 / sqrtf(.):
+    both correctly rounded, 2 u.  The pair's bounds: e_mu, and rel_r rstd."""
+    D = x.shape[-1]
+    st = ln_stats_bound(x, eps, D + 2, D + 3, 2.0)
+    return torch.cat([st["mu"], st["rstd"]], -1), torch.cat([st["e_mu"], 1.01 * st["rel_r"] * st["rstd"]], -1)
+
+
+def sincos_ref(arg32):
+    """sinf / cosf of an fp32 argument -> (sin, cos, bound_sin, bound_cos): the float64 sine and cosine OF THE FP32 VALUE and
+    SINCOS_ULPS ulps of the fp32 result.  The kernels form the argument as ONE fp32 product (t * freqs, p * freqs), which the
+    caller restates exactly; nothing else is rounded."""
+    a = _t64(arg32)
+    s, c = torch.sin(a), torch.cos(a)
+    return s, c, SINCOS_ULPS * ulp32(s), SINCOS_ULPS * ulp32(c)
+
+
+def silu_f32_ref(x):
+    """primx_silu_f32 on FINITE x -> (exact, bound).  x / (1 + expf(-x)): -x is exact; expf carries EXP_ULPS ulp = 2 EXP_ULPS u
+    relative, which reaches the quotient through e / (1 + e) = 1 - sigma(x); the sum and the (correctly rounded) division add u
+    each:   bound = |silu| u (2 EXP_ULPS (1 - sigma) + 2)  (x 1.01, + one subnormal spacing).
+    Below -LN_FLT_MAX expf(-x) is +inf and the result -0 (silu64; torch's fp32 silu does the same).  Where exp(-x) lies within
+    expf's error and half an ulp of the largest fp32 value - |x + LN_FLT_MAX| <= (2 EXP_ULPS + 1) u, the relative error of exp being
+    the absolute one of x - either side may happen: the bound there adds the finite value's whole magnitude |x| / FLT_MAX."""
+    xd = _t64(x)
+    sig = torch.sigmoid(xd)
+    fin = xd * sig
+    over = -xd > LN_FLT_MAX
+    exact = torch.where(over, torch.full_like(xd, -0.0), fin)
+    bound = 1.01 * exact.abs() * U32 * (2.0 * EXP_ULPS * (1.0 - sig) + 2.0) + 2.0 ** -149
+    edge = (-xd - LN_FLT_MAX).abs() <= (2.0 * EXP_ULPS + 1.0) * U32
+    bound = torch.where(edge, 1.01 * xd.abs() / FLT_MAX + bound, bound)
+    return exact, bound
+
+
+def check_bound(got, exact, bound, what="") -> float:
+    """Every element of `got` finite and within `bound` of `exact` - no slack factor.  Returns max |err| / bound."""
+    g = _t64(got).to(exact.device).reshape(exact.shape)
+    assert bool(torch.isfinite(g).all()), f"{what}: non-finite output"
+    err = (g - exact).abs()
+    bad = err > bound
+    ratio = float((err / torch.clamp(bound, min=1e-300)).max()) if err.numel() else 0.0
+    if bool(bad.any()):
+        idx = [tuple(int(i) for i in r) for r in torch.nonzero(bad)[:8].tolist()]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {err.numel()} elements beyond the fp32 bound, worst {ratio:.3g} x, first at {idx}")
+    return ratio
+
+
+def rms_ratio(got, restated, exact) -> float:
+    """rms |got - exact| over max(rms |restated - exact|, u rms |exact|): the kernel's error against the numpy-fp32 restatement's
+    on the same inputs (the floor keeps a restatement that happens to be exact - one key, K = 4 - from being a zero)."""
+    ex = _t64(exact)
+    g, r = _t64(got).to(ex.device).reshape(ex.shape), _t64(restated).to(ex.device).reshape(ex.shape)
+    rms = lambda t: float(torch.sqrt(torch.mean(t * t))) if t.numel() else 0.0
+    floor = max(rms(r - ex), U32 * rms(ex), 1e-300)
+    return rms(g - ex) / floor
+
+
+RMS_MARGIN = 2.0   # NOT measured: a serial MFMA / fmaf chain against BLAS's blocked order, v_exp_f32 against libm
+
+
+def check_rms(got, restated, exact, what="", margin=RMS_MARGIN) -> float:
+    ratio = rms_ratio(got, restated, exact)
+    assert ratio <= margin, f"{what}: rms error {ratio:.3g} x the fp32 restatement's (margin {margin})"
+    return ratio
+
+
+def hold_fp32(got, restated, exact, bound, what="", margin=RMS_MARGIN):
+    """Both criteria of an fp32 entry point: every element inside the rigorous bound, and the rms error no more than `margin`
+    times the restatement's.  Returns (max |err| / bound, rms ratio)."""
+    a = check_bound(got, exact, bound, what)
+    b = check_rms(got, restated, exact, what, margin)
+    return a, b
+
+
+def timestep_embedding_ref(t, freqs):
+    """primx_timestep_embedding -> (exact [B, 2 half], bound): [cos(arg) | sin(arg)], arg = fl(float(t) * freqs) - the ONE fp32
+    product of the kernel, restated exactly (an IEEE fp32 product is the same on every machine)."""
+    arg = t.to(torch.float32)[:, None] * freqs.to(torch.float32)[None, :]
+    s, c, bs, bc = sincos_ref(arg)
+    return torch.cat([c, s], -1), torch.cat([bc, bs], -1)
+
+
+def point_features_ref(x, freqs):
+    """primx_point_features -> (exact [T, round_up(6 F + 3, 4)], bound): [sin(p_d f_k) (3 F) | cos (3 F) | p (3) | 0 padding], column
+    d F + k, p = x[:, 1:4], arguments one fp32 product.  The pass-through columns and the padding are bit-exact: bound 0."""
+    T, F = x.shape[0], freqs.shape[0]
+    p = x[:, 1:4].to(torch.float32)
+    arg = (p[:, :, None] * freqs.to(torch.float32)[None, None, :]).reshape(T, 3 * F)
+    s, c, bs, bc = sincos_ref(arg)
+    width = (6 * F + 3 + 3) // 4 * 4
+    pad = torch.zeros(T, width - 6 * F - 3, dtype=torch.float64, device=x.device)
+    z3 = torch.zeros(T, 3, dtype=torch.float64, device=x.device)
+    return torch.cat([s, c, p.double(), pad], -1), torch.cat([bs, bc, z3, pad], -1)
+
+
+def vit_tokens_ref(patches, cls, pos, reg, pos_shift=1):
+    """primx_vit_tokens in torch fp32: [cls + pos[0] | reg | patches + pos[1:]] - one fp32 addition per element, so the kernel is
+    held to it bit for bit.  pos_shift = 0: the injected fault pos[i] for pos[1 + i]."""
+    B, n, D = patches.shape
+    rows = [(cls + pos[0])[None, None].expand(B, 1, D)]
+    if reg is not None and reg.shape[0]:
+        rows.append(reg[None].expand(B, -1, -1))
+    rows.append(patches + pos[pos_shift:pos_shift + n][None])
+    return torch.cat(rows, 1)
+
+
+# inputs of the fp32 contract tests (tests/test_fp32_contract_cpu.py on the CPU, tests/test_hip_fp32_contract.py on the device)
+def gemm_inputs(seed, M, N, K, device):
+    g = torch.Generator(device=device).manual_seed(seed)
+    A = torch.randn(M, K, device=device, generator=g)
+    W = torch.randn(N, K, device=device, generator=g) * K ** -0.5
+    b = torch.randn(N, device=device, generator=g) * 0.1
+    return A, W, b, g
+
+
+def qkv_inputs(seed, B, Mq, Mk, H, dh, sigma, device):
+    """Logits q . k / sqrt(dh) of standard deviation sigma."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    q = torch.randn(B, Mq, H, dh, device=device, generator=g) * sigma
+    k = torch.randn(B, Mk, H, dh, device=device, generator=g)
+    v = torch.randn(B, Mk, H, dh, device=device, generator=g)
+    return q, k, v
+
+
+LN_BANDS = [(3.0, 0.5), (1.0, 20.0), (1e-3, 1.0), (1e3, -1e4)]     # (spread, offset): the mean dwarfs the spread in three of them
+
+
+def ln_inputs(seed, rows, D, spread, offset, nb, device):
+    """x [rows, D] and one wide modulation buffer [nb, 3 D] whose column slices [:, :D] / [:, 2 D:] are shift / scale."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    x = torch.randn(rows, D, device=device, generator=g) * spread + offset
+    mod = torch.randn(nb, 3 * D, device=device, generator=g) * 0.3
+    return x, mod
+
+
+def heads_of(t):
+    """[B, M, H, dh] -> [B H, M, dh] numpy fp32 (attn_f32_restate's layout)."""
+    B, M, H, dh = t.shape
+    return t.detach().permute(0, 2, 1, 3).reshape(B * H, M, dh).cpu().numpy().astype(np.float32)
+
+
+def unheads(a, B, H):
+    """[B H, M, dh] numpy -> [B, M, H, dh] torch."""
+    G, M, dh = a.shape
+    return torch.from_numpy(np.ascontiguousarray(a)).reshape(B, H, M, dh).permute(0, 2, 1, 3)
+
+
+def chain_factor(A, W, bias=None, rows=16, cols=256) -> float:
+    """How much larger the rms error of a SERIAL fp32 chain of K fused multiply-adds (what gemm_f32_kernel's MFMA chain and
+    linear_f32_kernel's fmaf loop are) is than that of the BLAS product the GEMM tests use as their restatement, on a
+    rows x cols block of the same operands: >= 1.  BLAS sums K in blocks and several accumulators, so its error grows with the
+    block length, the chain's with sqrt(K): emulated on the CPU the ratio is 1.0 at K = 68, 1.4 - 2.4 at K = 768 / 1152 and 3.9 - 4.6
+    at 4608 (it depends on the BLAS kernel the shape selects).  The rms criterion of a chain kernel is therefore RMS_MARGIN x this factor: "no worse than twice a correct chain".
+    Each step is emulated as fp32(acc + a w) with the product and the sum in float64 (a double rounding happens for about one
+    step in 2^29 and moves one element by half an ulp)."""
+    a = _t64(A)[:rows].cpu().numpy()
+    w = _t64(W)[:cols].cpu().numpy()
+    b = _t64(bias)[:cols].cpu().numpy() if bias is not None else np.zeros(w.shape[0])
+    exact = a @ w.T + b
+    acc = np.zeros(exact.shape, np.float32)
+    for k in range(a.shape[1]):
+        acc = (acc.astype(np.float64) + a[:, k:k + 1] * w[None, :, k]).astype(np.float32)
+    chain = (acc.astype(np.float64) + b).astype(np.float32)
+    blas = (torch.from_numpy(a.astype(np.float32)) @ torch.from_numpy(w.astype(np.float32)).t() + torch.from_numpy(b.astype(np.float32))).numpy()
+    rms = lambda t: float(np.sqrt(np.mean((t.astype(np.float64) - exact) ** 2)))
+    return max(1.0, rms(chain) / max(rms(blas), U32 * float(np.sqrt(np.mean(exact ** 2))), 1e-300))

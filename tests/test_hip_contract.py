@@ -531,76 +531,11 @@ def test_linear_f32out_rigorous_bound(ops, dtype):
 
 
 # ------------------------------------------------------------------------------------------------ attention
-# attn_kernel / attn64_kernel are not one-rounding operations.  csrc/attention.hip documents what they approximate:
-#   dh = 72 (Q carries the mask / max columns): Q pre-scaled by c = scale log2(e) and rounded to 16 bits; the running max held
-#     as two 16-bit halves; P = exp2(s - m) packed round-toward-zero (fp16) / truncated (bf16) and used for BOTH the numerator
-#     and the denominator (the all-ones row of V^T);
-#   dh = 32 / 64 and the 64-token kernel: logits scaled in fp32; P rounded to nearest for the numerator, the denominator summed
-#     from the unrounded fp32 P;
-#   fp32 O and row sum, one reciprocal, one final rounding.
-# With w_j = softmax weights, out = sum_j w_j v_j, and relative weight errors eta_j, the output moves by
-#   sum_j w_j eta_j (v_j - out)   when numerator and denominator carry the same eta_j (a common factor cancels), and
-#   sum_j w_j eta_j v_j           when only the numerator does.
-# So, per element:  bound = 0.5 ulp16(out) + ln2 sum_j w_j |v_j - out| ds_j + dP sum_j w_j A_j + floor + fp32 terms, with
-#   ds_j = (u_q + (dh + 4) 2^-24) sum_d |q_d c k_jd| + 2^-22 max_j |s_j|   (exp2 units: Q's rounding u_q = 2^-11 / 2^-8 on the
-#          dh = 72 path, 0 else; fp32 accumulation of dh + 3 products and of c; the max's split and the exp2 argument),
-#   dP   = the pack's relative error (2^-10 / 2^-7 toward zero on the dh = 72 path, 2^-11 / 2^-8 to nearest else) + 2^-22 (v_exp),
-#   A_j  = |v_j - out| (same P in both sums) or |v_j| (numerator only),
-#   floor = 2^-24 sum_j A_j / L for fp16 (subnormal / flushed P below 2^-14 against the running max; L = sum_j 2^(s_j - max)),
-#   fp32 = gamma_nkv (sum_j w_j |v_j| + |out|) + 2^-22 |out|   (accumulation of O and of the row sum; the reciprocal and product).
-ATTN_SLACK = 2.0
-
-
-def _attn_bound(q, k, v, scale, dtype, same_p):
-    """Exact output [B, Mq, H, dh] and the per-element bound above (float64 on the device)."""
-    B, Mq, H, dh = q.shape
-    nkv = k.shape[1]
-    c = cr.f32(cr.f32(scale) * 1.4426950408889634)
-    u_q = (2.0 ** -11 if dtype == F16 else 2.0 ** -8) if same_p else 0.0      # (same_p: the dh = 72 path)
-    dP = ((2.0 ** -10 if dtype == F16 else 2.0 ** -7) if same_p else (2.0 ** -11 if dtype == F16 else 2.0 ** -8)) + 2.0 ** -22
-    gam = nkv * 2.0 ** -24 / (1 - nkv * 2.0 ** -24)
-    outs, bounds = torch.empty(B, Mq, H, dh, dtype=torch.float64, device=DEV), torch.empty(B, Mq, H, dh, dtype=torch.float64, device=DEV)
-    for b in range(B):
-        for h in range(H):
-            Q, K, V = q[b, :, h].double(), k[b, :, h].double(), v[b, :, h].double()
-            S2 = (Q @ K.t()) * cr.f32(scale) * 1.4426950408889634            # exact logits, exp2 units
-            m = S2.max(1, keepdim=True).values
-            Pm = torch.pow(2.0, S2 - m)
-            L = Pm.sum(1, keepdim=True)
-            w = Pm / L
-            out = w @ V
-            ds = (u_q + (dh + 4) * 2.0 ** -24) * ((Q.abs() @ K.abs().t()) * c) + 2.0 ** -22 * S2.abs().max(1, keepdim=True).values
-            D = (V[None] - out[:, None]).abs()                                 # [Mq, nkv, dh]
-            A = D if same_p else V.abs()[None].expand_as(D)
-            E = np.log(2.0) * torch.einsum("qj,qjd->qd", w * ds, D) + dP * torch.einsum("qj,qjd->qd", w, A)
-            if dtype == F16:
-                E = E + 2.0 ** -24 * A.sum(1) / L
-            E = E + gam * (w @ V.abs() + out.abs()) + 2.0 ** -22 * out.abs()
-            outs[b, :, h], bounds[b, :, h] = out, E
-            del D, A
-    return outs, bounds
-
-
-def _attn_check(got, q, k, v, scale, dtype, same_p, what):
-    out, E = _attn_bound(q, k, v, scale, dtype, same_p)
-    out_np = out.cpu().numpy()
-    bound = 0.5 * cr.ulp16(out_np, dtype) + E.cpu().numpy()
-    g = cr._f64(got).reshape(out_np.shape)
-    err = np.abs(g - out_np)
-    ratio = float(np.max(err / bound))
-    print(f"attention {what} {dtype}: max |err| / bound = {ratio:.3f}")
-    assert ratio <= ATTN_SLACK, f"attention {what} {dtype}: error {ratio:.3f} x the derived bound"
-    # no bias: the mean signed error in ulps of the result, over the elements that do not cancel to near zero.  Asserted where
-    # every documented approximation is unbiased (P rounded to nearest).  The dh = 72 path packs P toward zero by design: a key
-    # at the running max keeps p = 1 exactly while every other key loses 2^-11 (fp16) / 2^-8 (bf16) of its weight on average,
-    # which pulls the output towards the dominant key's value - inside the bound above, but a bias; it is reported only.
-    rms = float(np.sqrt(np.mean(out_np ** 2)))
-    sel = np.abs(out_np) >= 0.25 * rms
-    bias = float(np.mean((g - out_np)[sel] * np.sign(out_np[sel]) / cr.ulp16(out_np[sel], dtype)))
-    print(f"attention {what} {dtype}: mean signed error {bias:+.3f} ulp")
-    if not same_p:
-        assert abs(bias) <= cr.BIAS_LIMIT, f"attention {what} {dtype}: biased by {bias:.3f} ulp"
-    return ratio
+# attn_kernel / attn64_kernel are not one-rounding operations: what they approximate, the per-element bound derived from it and the
+# check (ATTN_SLACK, the bias criterion) live in tests/contract_ref.py next to the fp32 kernel's form of the same bound.
+ATTN_SLACK = cr.ATTN_SLACK
+_attn_bound = cr.attn_bound
+_attn_check = cr.attn_check
 
 
 def _qkv(seed, B, Mq, Mk, H, dh, sigma, dtype):
