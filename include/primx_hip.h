@@ -14,6 +14,36 @@
  *   - `dtype` selects the 16-bit storage/MFMA-input type of activations and weights:
  *     PRIMX_F16 or PRIMX_BF16.  Accumulation is always fp32.
  *
+ * Memory contract (held entry point by entry point by tests/test_hip_footprint.py: guard bytes around every buffer,
+ * snapshots of every const operand, every torch.empty of the Python hosts poisoned with 0xFF and with 0x00 bytes)
+ *   - a pointer declared const is never written.
+ *   - a kernel reads and writes inside the extents its entry point documents and nowhere else: an [M, N] output has no
+ *     row M and no column N, however ragged the last tile; an output sized by a count the library reported (nverts,
+ *     ntris, n_out, the counts of the mesh stages, n of primx_texbake_compact) ends at its last element; a padded attention
+ *     operand layout is written at [token < n, d < dh] only (its pads, mask columns and all-ones V^T row keep what the
+ *     caller put there, and primx_attention[_bcast] reads but never writes Q, K and V^T).
+ *   - ENTRY CONTENTS.  Every output and every scratch argument may hold ANY bytes at entry (NaN patterns included): no
+ *     kernel reads one before it has written it, and the results are bit-identical whatever it held.  That covers
+ *       * the `ws` of every primx_*_workspace query (mcubes, texbake components / raster / fill, meshclean, meshdecim),
+ *         used at exactly the queried size.  What must SURVIVE between calls: the mcubes workspace from
+ *         primx_mcubes_count to primx_mcubes_emit, the raster workspace from primx_texbake_raster to
+ *         primx_texbake_compact, and - the caller keeps it untouched, as the Python host does - the one meshclean
+ *         workspace from primx_meshclean_merge to primx_meshclean_fans of a mesh and the one meshdecim workspace over
+ *         the rounds of a mesh.  The first call on a workspace accepts any contents; a workspace may be reused for
+ *         another mesh, lattice or atlas without clearing it;
+ *       * a16, part and center_out of the LayerNorm fold; xn, att, hid, center0, center1 and part of PrimxDitForwardFold
+ *         (center / center0 / center1 are read only after a row-stats or consumer call of the same forward wrote them);
+ *       * m1 of primx_meshdecim_select, the `part` statistics of primx_convtranspose_s4_packed, the packed weight
+ *         images of the *_pack entry points (written in full: exactly the image's bytes), totals / counts.
+ *     The exceptions - arguments that must hold defined values at entry - are documented in-place operands:
+ *       * x of the gated residual GEMMs, `out` of primx_gemm_f32 with a gate, h of PrimxDitForwardFold, p / Q / f of
+ *         primx_meshdecim_collapse (read and updated);
+ *       * `sync` of primx_linear_gate_residual_ln: zero at entry, zero again when the launch has finished;
+ *       * the pads of attention operand buffers (Qc, Qs, Ks, Vs, Kc, Vc, Kb, Vb): as ops.alloc_heads of the Python
+ *         host leaves them (zero; the query / key-mask columns dh .. dh + 2; the all-ones V^T row dh) - a buffer with no
+ *         pad row and no pad column (DP == dh, n_pad == n, not KROWS) may hold anything;
+ *       * first / last of primx_meshdecim_edges: 0 for vertices no face references (see there).
+ *
  * Each entry cites the reference code it replaces (paths relative to the 3DTopia-XL repo).
  * The reference has no native FFI on this path (it is PyTorch + xFormers); its one functional
  * seam is xformers.ops.memory_efficient_attention (models/attention.py:17,54,109), and the
