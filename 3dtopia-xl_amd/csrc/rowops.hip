@@ -233,6 +233,9 @@ extern "C" int primx_timestep_embedding(const int64_t* t, const float* freqs, fl
                                         void* stream) {
     PRIMX_REQUIRE(t && freqs && emb, "primx_timestep_embedding: null pointer");
     PRIMX_REQUIRE(B > 0 && dim > 0 && dim % 2 == 0, "primx_timestep_embedding: dim must be even");
+    // (the kernel's flat index idx = b * (dim / 2) + k is an int)
+    PRIMX_REQUIRE((int64_t)B * (dim / 2) < ((int64_t)1 << 31), "primx_timestep_embedding: B * dim / 2 must be < 2^31 (got B = %d, dim = %d)",
+                  B, dim);
     const int n = B * (dim / 2);
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, freqs,
                        emb, B, dim);
@@ -295,6 +298,8 @@ extern "C" int primx_point_features(const float* x, int64_t row_stride, const fl
     PRIMX_REQUIRE(x && freqs && feat, "primx_point_features: null pointer");
     PRIMX_REQUIRE(T > 0 && F > 0 && row_stride >= 4 && feat_stride >= 6 * F + 3,
                   "primx_point_features: need T, F > 0, at least 4 channels per token and feat_stride >= 6F+3");
+    // (the kernel's flat index idx = t * 3 F + c is an int)
+    PRIMX_REQUIRE((int64_t)T * 3 * F < ((int64_t)1 << 31), "primx_point_features: 3 * T * F must be < 2^31 (got T = %d, F = %d)", T, F);
     const int n = T * 3 * F;
     hipLaunchKernelGGL(point_features_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, row_stride,
                        freqs, feat, feat_stride, T, F);

@@ -44,6 +44,25 @@
  *         pad row and no pad column (DP == dh, n_pad == n, not KROWS) may hold anything;
  *       * first / last of primx_meshdecim_edges: 0 for vertices no face references (see there).
  *
+ * Extents (held by tests/test_hip_extent.py: every entry point below once on operands of more than 2^31 elements, every
+ * element against the same call on slices of 2048 primitives, probe primitives against float64)
+ *   - counts are `int` (P, M, N, K, V, C, rows per batch, B x H of attention) or int64_t (n of the elementwise kernels, rows
+ *     of primx_latent_denorm); each must fit its type.  PRODUCTS of them may pass 2^31 - a decode chunk of 16384 primitives
+ *     has a [P, 512, 256] activation of exactly 2^31 elements - and the kernels form them in 64 bits:
+ *       * the VAE decoder family (primx_groupnorm_silu, primx_conv_in, primx_conv3d_k3, primx_conv3d_s4_packed,
+ *         primx_conv3d_s8_packed, primx_conv3d_s8_fused, primx_conv3d_s8c32_packed, primx_convtranspose_k2s2,
+ *         primx_convtranspose_s4_packed, primx_vae_output): primitive * V * C, and the `part` statistics per primitive;
+ *       * the GEMM family (primx_linear, _residual, _gate_residual[_ln], _heads and the fold forms): row * K, row * N and the
+ *         head-layout offsets of every epilogue.  One kernel keeps 32-bit BYTE offsets: the 128-byte ring of the 256 x 288
+ *         tile; the dispatch takes it only while M * K < 2^31 and N * K < 2^31 and falls back to the 64-byte ring (64-bit
+ *         offsets, same results to the contract) from there on - a choice of kernel, not a limit of the entry point;
+ *       * primx_attention with the compact 64-token operands: (batch * H + head) * 64 * DP;
+ *       * the elementwise kernels (primx_cast16, primx_silu_cast, primx_silu_f32, primx_cfg_combine, primx_latent_denorm):
+ *         a 64-bit grid-stride index.
+ *   - REFUSED with PRIMX_EINVAL before any launch, because the kernel's flat index is an `int`: primx_timestep_embedding with
+ *     B * (dim / 2) >= 2^31 and primx_point_features with 3 * T * F >= 2^31 (thousands of times the shipped sizes).  The mesh
+ *     entry points state their own limits (3 nx ny nz, 3 V, 9 F, 6 V < 2^31) where they are declared.
+ *
  * Each entry cites the reference code it replaces (paths relative to the 3DTopia-XL repo).
  * The reference has no native FFI on this path (it is PyTorch + xFormers); its one functional
  * seam is xformers.ops.memory_efficient_attention (models/attention.py:17,54,109), and the

@@ -66,6 +66,11 @@ def test_argument_validation_without_gpu(lib):
     assert h.primx_linear_gate_residual_ln(1, 1, None, 1, 0, 1, 256, 1152, 64, 256, None, None, 0, 1, 1e-6, None, 0, 1, None, 0, None) == -1
     assert h.primx_linear_gate_residual_ln(1, 1, None, 1, 0, 1, 256, 1152, 64, 256, 1, 1, 0, 1, 1e-6, 1, 3, 1, None, 0, None) == -1
     assert b"sync" in h.primx_last_error()
+    # extents: launchers whose kernels index with an int refuse a product past 2^31 instead of wrapping (B * dim / 2; 3 * T * F)
+    assert h.primx_timestep_embedding(1, 1, 1, 1 << 20, 4096, None) == -1
+    assert b"2^31" in h.primx_last_error()
+    assert h.primx_point_features(1, 4, 1, 1, 1 << 20, 1 << 26, 16, None) == -1
+    assert b"2^31" in h.primx_last_error()
     with pytest.raises(lib.PrimxError):
         lib.check(-1, "primx_linear")
 

@@ -82,12 +82,13 @@ KERNELS = {
 def _check_rows(got, pre, ref, dtype, K, M, what, **kw):
     """check_contract over all rows, and separately over a ragged last 128-row tile (criteria 2 and 3 are statistics: a
     rounding error confined to the tail tile would vanish in the whole)."""
-    cr.check_contract(got, pre, ref, dtype, K, what=what, **kw)
+    rep = cr.check_contract(got, pre, ref, dtype, K, what=what, **kw)
     t0 = M - M % 128
     if M % 128 and M > 128:
         sl = lambda a: a[t0:] if np.ndim(a) == 2 else a
         kw = {k: sl(v) for k, v in kw.items()}
         cr.check_contract(cr._f64(got)[t0:], pre[t0:], ref[t0:], dtype, K, what=what + " (ragged tail tile)", **kw)
+    return rep
 
 
 def _operands(seed, M, N, K, dtype, band="normal", bias=True):
@@ -126,6 +127,40 @@ def _launched():
     return _lib.load().primx_last_gemm_kernel().decode()
 
 
+def check_linear(got, acc, dtype, K, M, act, scale, what):
+    """The contract check of one primx_linear output `got` ([M, N]; acc = the exact A W^T + bias): the arguments
+    test_gemm_contract uses (also called by tests/test_hip_extent.py on row blocks of far larger operands)."""
+    pre, ref = cr.linear_ref(acc, dtype, act, scale)
+    one = act == 0 and cr.f32(scale) == 1.0                 # one rounding, no element-wise stage
+    return _check_rows(got, pre, ref, dtype, K, M, what, acc=acc, gain=1.2 * abs(scale),
+                       inner=(0.0 if one else 1.2 * abs(cr.f32(scale)) * cr.ulp16(acc, dtype)), ew_ulps=(0.0 if one else 4.0))
+
+
+def check_linear_residual(got, acc, dtype, K, M, res, scale, what):
+    """The same for primx_linear_residual: ((A W^T + bias) + res) * scale with one rounding (res may be None)."""
+    pre, ref = cr.linear_residual_ref(acc, dtype, res, scale)
+    return _check_rows(got, pre, ref, dtype, K, M, what, acc=pre, ew_ulps=(2.0 if res is not None else 0.0))
+
+
+def check_gate_increment(x, acc, gate_rows, dtype, K, M, what):
+    """primx_linear_gate_residual on x_in = 0: the fp32 x holds the 16-bit increment cast16(gate * cast16(A W^T + bias))
+    itself (gate_rows [M, N] = the gate of each row)."""
+    pre, ref = cr.gate_residual_ref(acc, gate_rows, dtype)
+    xg = cr._f64(x)
+    assert np.array_equal(cr.round16(xg, dtype), xg), f"{what}: the increment is not a 16-bit value"
+    return _check_rows(xg, pre, ref, dtype, K, M, f"{what} increment", acc=acc, gain=gate_rows, inner=np.abs(gate_rows) * cr.ulp16(acc, dtype))
+
+
+def check_heads_segment(got, a_seg, dtype, K, first, scale0, what):
+    """One segment of primx_linear_heads (got, a_seg: [B, n, H, dh]; a_seg = the exact projection): segment 0 is scaled by
+    scale0 AFTER its rounding, the others are rounded once."""
+    if first:
+        qpre = cr.f32(scale0) * cr.round16(a_seg, dtype)
+        return cr.check_contract(got, qpre, cr.round16(qpre, dtype), dtype, K, acc=a_seg, gain=scale0, ew_ulps=1.0,
+                                 inner=scale0 * cr.ulp16(a_seg, dtype), what=what)
+    return cr.check_contract(got, a_seg, cr.round16(a_seg, dtype), dtype, K, what=what)
+
+
 def _check_gemm_case(ops, dtype, case, reached, band="normal"):
     op, M, N, K = case["op"], case["M"], case["N"], case["K"]
     seed = _seed(op, M, N, K, band)
@@ -146,18 +181,14 @@ def _check_gemm_case(ops, dtype, case, reached, band="normal"):
         for act, scale in case.get("acts", [(0, 1.0)]):
             got = ops.linear(A, W, b, act=act, out_scale=scale)
             note()
-            pre, ref = cr.linear_ref(acc, dtype, act, scale)
-            one = act == 0 and cr.f32(scale) == 1.0                 # one rounding, no element-wise stage
-            _check_rows(got, pre, ref, dtype, K, M, f"{what} act={act} scale={scale}", acc=acc, gain=1.2 * abs(scale),
-                        inner=(0.0 if one else 1.2 * abs(cr.f32(scale)) * cr.ulp16(acc, dtype)), ew_ulps=(0.0 if one else 4.0))
+            check_linear(got, acc, dtype, K, M, act, scale, f"{what} act={act} scale={scale}")
     elif op == "residual":
         g = torch.Generator(device=DEV).manual_seed(seed + 1)
         res = (torch.randn(M, N, device=DEV, generator=g) * 0.3 * float(np.sqrt(np.mean(acc ** 2)))).to(dtype)
         for r, sc in ((res, 0.70710678), (None, 1.0)):
             got = ops.linear_residual(A, W, b, r, sc)
             note()
-            pre, ref = cr.linear_residual_ref(acc, dtype, r, sc)
-            _check_rows(got, pre, ref, dtype, K, M, f"{what} res={r is not None}", acc=pre, ew_ulps=(2.0 if r is not None else 0.0))
+            check_linear_residual(got, acc, dtype, K, M, r, sc, f"{what} res={r is not None}")
     elif op in ("gate", "gate_ln"):
         rpb = case["rpb"]
         nb = (M + rpb - 1) // rpb
@@ -166,8 +197,6 @@ def _check_gemm_case(ops, dtype, case, reached, band="normal"):
         gate, shift, scl = mod[:, :N], mod[:, N:2 * N], mod[:, 2 * N:]
         rows = np.arange(M) // rpb
         gate_rows = gate.double().cpu().numpy()[rows]
-        pre, ref = cr.gate_residual_ref(acc, gate_rows, dtype)
-        kw = dict(acc=acc, gain=gate_rows, inner=np.abs(gate_rows) * cr.ulp16(acc, dtype))
         x = torch.zeros(M, N, device=DEV)
         if op == "gate":
             ops.linear_gate_residual(A, W, b, gate, x, rpb)
@@ -178,9 +207,7 @@ def _check_gemm_case(ops, dtype, case, reached, band="normal"):
             ops.linear_gate_residual(A, W, b, gate, x, rpb, ln=(shift, scl, lnout, 1e-6, sync))
             note()
         # x_in = 0: the fp32 x receives the 16-bit increment itself, exactly
-        xg = x.double().cpu().numpy()
-        assert np.array_equal(cr.round16(xg, dtype), xg), f"{what}: the increment is not a 16-bit value"
-        _check_rows(xg, pre, ref, dtype, K, M, f"{what} increment", **kw)
+        check_gate_increment(x, acc, gate_rows, dtype, K, M, what)
         if op == "gate_ln":
             lpre, lref = cr.layernorm_modulate_ref(x, shift.double().cpu().numpy()[rows], scl.double().cpu().numpy()[rows], dtype)
             cr.check_contract(lnout, lpre, lref, dtype, N, ew_ulps=8.0, what=f"{what} LayerNorm tail")
@@ -202,15 +229,10 @@ def _check_gemm_case(ops, dtype, case, reached, band="normal"):
         ops.linear_heads(A, W, b, n, H, dh, kinds, dsts, dsts[0].shape[2], scale0=scale0)
         note()
         a5 = acc.reshape(B, n, len(kinds), H, dh)
-        y16 = cr.round16(a5, dtype)
         for s_, (kd, dst) in enumerate(zip(kinds, dsts)):
             got = unpack_vt(dst, n, dh) if kd == HEADS_VT else unpack_rows(dst, n, dh)
-            if s_ == 0:                                                  # segment 0: scaled after the rounding
-                qpre = cr.f32(scale0) * y16[:, :, 0]
-                cr.check_contract(got, qpre, cr.round16(qpre, dtype), dtype, K, acc=a5[:, :, 0], gain=scale0, ew_ulps=1.0,
-                                  inner=scale0 * cr.ulp16(a5[:, :, 0], dtype), what=f"{what} segment 0 (scaled after rounding)")
-            else:
-                cr.check_contract(got, a5[:, :, s_], y16[:, :, s_], dtype, K, what=f"{what} segment {s_} kind {kd}")
+            check_heads_segment(got, a5[:, :, s_], dtype, K, s_ == 0, scale0,
+                                f"{what} segment 0 (scaled after rounding)" if s_ == 0 else f"{what} segment {s_} kind {kd}")
     else:
         raise AssertionError(op)
 
@@ -346,14 +368,21 @@ def _gn_params(seed, C):
     return torch.randn(C, device=DEV, generator=g) * 0.2 + 1.0, torch.randn(C, device=DEV, generator=g) * 0.2
 
 
+def check_groupnorm_silu(got, x, gam, bet, groups, silu, dtype):
+    """The contract check of a primx_groupnorm_silu output for the operands it was computed from (x [P, V, C], eps 1e-5); the
+    check functions below follow the same pattern and are also run by tests/test_hip_extent.py on single primitives of far
+    larger batches."""
+    _, V, C = x.shape
+    pre, ref = cr.groupnorm_silu_ref(x, gam, bet, groups, 1e-5, silu, dtype)
+    return cr.check_contract(got, pre, ref, dtype, V * C // groups, ew_ulps=8.0, what=f"groupnorm_silu C={C} V={V}")
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("C,V,groups,silu", [(256, 64, 32, True), (256, 512, 32, True), (32, 512, 32, True), (64, 27, 8, False)])
 def test_groupnorm_silu_contract(ops, dtype, C, V, groups, silu):
     x = _cl_rand(C + V, 3, V, C, dtype, 1.3, 0.2)
     gam, bet = _gn_params(C, C)
-    got = ops.groupnorm_silu(x, gam, bet, groups, 1e-5, silu)
-    pre, ref = cr.groupnorm_silu_ref(x, gam, bet, groups, 1e-5, silu, dtype)
-    cr.check_contract(got, pre, ref, dtype, V * C // groups, ew_ulps=8.0, what=f"groupnorm_silu C={C} V={V}")
+    check_groupnorm_silu(ops.groupnorm_silu(x, gam, bet, groups, 1e-5, silu), x, gam, bet, groups, silu, dtype)
 
 
 def _conv_w(seed, Cout, Cin, dtype):
@@ -362,6 +391,13 @@ def _conv_w(seed, Cout, Cin, dtype):
     w = torch.randn(Cout, Cin, 3, 3, 3, device=DEV, generator=g) * (27 * Cin) ** -0.5
     b = (torch.randn(Cout, device=DEV, generator=g) * 0.2).to(dtype)
     return _conv_weight_as_gemm(w, dtype), b
+
+
+def check_conv3d_k3(got, acc, dtype, K, res, res_scale, what):
+    """conv3d_k3 (any route): ((conv + bias) + res) * res_scale with one rounding; acc [P, V, Cout] = the exact conv + bias
+    (cr.conv3d_k3_acc), res None or the residual operand."""
+    pre, ref = cr.linear_residual_ref(acc, dtype, res, res_scale)
+    return cr.check_contract(got, pre, ref, dtype, K, what=what)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -384,11 +420,9 @@ def test_conv3d_k3_contract(ops, dtype, Cin, Cout, S, P, packed):
         routes.append((packed, wp))
     for route, w in routes:
         got = ops.conv3d_k3(x, wk, b, S, res=res, res_scale=0.5 ** 0.5, Wp=w)
-        pre, ref = cr.linear_residual_ref(acc, dtype, res, 0.5 ** 0.5)
-        cr.check_contract(got, pre, ref, dtype, K, what=f"conv3d_k3 {route} {Cin}->{Cout} @{S}")
+        check_conv3d_k3(got, acc, dtype, K, res, 0.5 ** 0.5, f"conv3d_k3 {route} {Cin}->{Cout} @{S}")
         got = ops.conv3d_k3(x, wk, None, S, Wp=w)
-        pre = acc - b.double().cpu().numpy()
-        cr.check_contract(got, pre, cr.round16(pre, dtype), dtype, K, what=f"conv3d_k3 {route} no bias")
+        check_conv3d_k3(got, acc - b.double().cpu().numpy(), dtype, K, None, 1.0, f"conv3d_k3 {route} no bias")
 
 
 def _flip_tolerance(a16, wk, dtype):
@@ -399,6 +433,13 @@ def _flip_tolerance(a16, wk, dtype):
     most |w| ulp16(a).  Allowance per output channel: 2 max_k |W[co, k]| max ulp16(a)."""
     wmax = np.abs(wk.double().cpu().numpy()).max(1)
     return 2.0 * wmax * float(np.max(cr.ulp16(a16, dtype)))
+
+
+def check_conv3d_s8c32_gn(got, acc, a16, wk, dtype, res, res_scale, Cout):
+    """The 8^3 / 32-channel kernel with the GroupNorm inside: acc = the exact convolution of a16 = round16(silu(GN(x)))."""
+    pre, ref = cr.linear_residual_ref(acc, dtype, res, res_scale)
+    return cr.check_contract(got, pre, ref, dtype, 27 * 32, ew_ulps=2.0, inner=_flip_tolerance(a16, wk, dtype),
+                             what=f"conv3d s8c32 gn Cout={Cout}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -417,9 +458,18 @@ def test_conv3d_s8c32_groupnorm_inside_contract(ops, dtype, Cout, P):
     acc = cr.conv3d_k3_acc(a16, wk, b, S).reshape(P, V, Cout)
     res = _cl_rand(14, P, V, Cout, dtype, float(np.sqrt(np.mean(acc ** 2))))
     got = ops.conv3d_k3(x, wk, b, S, res=res, res_scale=0.5 ** 0.5, Wp=wp, gn=(gam, bet, 1e-5))
-    pre, ref = cr.linear_residual_ref(acc, dtype, res, 0.5 ** 0.5)
-    cr.check_contract(got, pre, ref, dtype, 27 * Cin, ew_ulps=2.0, inner=_flip_tolerance(a16, wk, dtype),
-                      what=f"conv3d s8c32 gn Cout={Cout}")
+    check_conv3d_s8c32_gn(got, acc, a16, wk, dtype, res, 0.5 ** 0.5, Cout)
+
+
+def check_conv3d_s8_fused(t, sc, h8, gam, bet, wk, b1, wsc, bsc, dtype):
+    """conv3d_s8_fused's two outputs for the 16-bit upsample output h8 [P, 512, 256] they were computed from."""
+    P, _, C = h8.shape
+    _, a16 = cr.groupnorm_silu_ref(h8, gam, bet, 32, 1e-5, True, dtype)
+    acc = cr.conv3d_k3_acc(a16, wk, b1, 8).reshape(P, 512, 32)
+    r1 = cr.check_contract(t, acc, cr.round16(acc, dtype), dtype, 27 * C, inner=_flip_tolerance(a16, wk, dtype),
+                           what="conv3d_s8_fused conv1")
+    sacc = cr.gemm_acc(h8.reshape(P * 512, C), wsc, bsc).reshape(P, 512, 32)
+    return r1, cr.check_contract(sc, sacc, cr.round16(sacc, dtype), dtype, C, what="conv3d_s8_fused shortcut")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -440,12 +490,12 @@ def test_conv3d_s8_fused_contract(ops, dtype):
     h8, part = ops.convtranspose_k2s2(x, wt, bu, 4, Wp=ops.pack_convt_s4(wt), want_stats=True)
     wp = ops.pack_conv3(wk, C, Wsc=wsc)
     t, sc = ops.conv3d_s8_fused(h8, wp, b1, part, bu, gam, bet, 1e-5, bsc)
-    _, a16 = cr.groupnorm_silu_ref(h8, gam, bet, 32, 1e-5, True, dtype)
-    acc = cr.conv3d_k3_acc(a16, wk, b1, 8).reshape(P, 512, 32)
-    cr.check_contract(t, acc, cr.round16(acc, dtype), dtype, 27 * C, inner=_flip_tolerance(a16, wk, dtype),
-                      what="conv3d_s8_fused conv1")
-    sacc = cr.gemm_acc(h8.reshape(P * 512, C), wsc, bsc).reshape(P, 512, 32)
-    cr.check_contract(sc, sacc, cr.round16(sacc, dtype), dtype, C, what="conv3d_s8_fused shortcut")
+    check_conv3d_s8_fused(t, sc, h8, gam, bet, wk, b1, wsc, bsc, dtype)
+
+
+def check_convtranspose_k2s2(got, acc, dtype, Cin, what):
+    """k2s2 upsample, either form: acc = cr.convtranspose_k2s2_acc of the operands, one rounding."""
+    return cr.check_contract(got, acc, cr.round16(acc, dtype), dtype, Cin, what=what)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -457,12 +507,16 @@ def test_convtranspose_k2s2_contract(ops, dtype, P, S, Cin, Cout):
     wt = (torch.randn(8 * Cout, Cin, device=DEV, generator=g) * Cin ** -0.5).to(dtype)
     b = (torch.randn(Cout, device=DEV, generator=g) * 0.3).to(dtype)
     acc = cr.convtranspose_k2s2_acc(x, wt, b, S)
-    ref = cr.round16(acc, dtype)
-    cr.check_contract(ops.convtranspose_k2s2(x, wt, b, S), acc, ref, dtype, Cin, what="convtranspose_k2s2 GEMM form")
+    check_convtranspose_k2s2(ops.convtranspose_k2s2(x, wt, b, S), acc, dtype, Cin, "convtranspose_k2s2 GEMM form")
     wp = ops.pack_convt_s4(wt)
     if wp is not None:
         got, _ = ops.convtranspose_k2s2(x, wt, b, S, Wp=wp, want_stats=True)
-        cr.check_contract(got, acc, ref, dtype, Cin, what="convtranspose_k2s2 packed")
+        check_convtranspose_k2s2(got, acc, dtype, Cin, "convtranspose_k2s2 packed")
+
+
+def check_conv_in(got, z, pq_scale, pq_bias, W, b, S, dtype):
+    acc = cr.conv_in_acc(z, pq_scale, pq_bias, W, b, S)
+    return cr.check_contract(got, acc, cr.round16(acc, dtype), dtype, 27, ew_ulps=8.0, what=f"conv_in S={S}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -473,9 +527,7 @@ def test_conv_in_contract(ops, dtype, S, Cout):
     z = torch.randn(P, S ** 3, device=DEV, generator=g)
     W = torch.randn(Cout, 27, device=DEV, generator=g) * 0.2
     b = torch.randn(Cout, device=DEV, generator=g) * 0.2
-    got = ops.conv_in(z, 1.7, -0.3, W, b, S, dtype)
-    acc = cr.conv_in_acc(z, 1.7, -0.3, W, b, S)
-    cr.check_contract(got, acc, cr.round16(acc, dtype), dtype, 27, ew_ulps=8.0, what=f"conv_in S={S}")
+    check_conv_in(ops.conv_in(z, 1.7, -0.3, W, b, S, dtype), z, 1.7, -0.3, W, b, S, dtype)
 
 
 # ------------------------------------------------------------------------------------------------ fp32 outputs

@@ -11,6 +11,7 @@ from tests.util import max_abs, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+SILU_F32_TOL = 1e-6        # max-abs of silu_f32 against F.silu in float64, |x| ~ 2
 TOL32 = 1e-4
 
 
@@ -94,7 +95,7 @@ def test_layernorm_modulate_f32_and_silu(ops):
     out = ops.layernorm_modulate_f32(x.to(DEV), md[:, :D], md[:, D:], n, 1e-6)
     assert rel_l2(out, ref.view(B * n, D)) < 1e-6
     t = synth.tensor(5, "t", (3, 1152), 2.0)
-    assert max_abs(ops.silu_f32(t.to(DEV)), torch.nn.functional.silu(t.double())) < 1e-6
+    assert max_abs(ops.silu_f32(t.to(DEV)), torch.nn.functional.silu(t.double())) < SILU_F32_TOL
 
 
 @pytest.mark.parametrize("case", [0, 1])

@@ -12,6 +12,13 @@ from tests.util import max_abs, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+# rel-L2 between two routes of one operation that round the same fp32 sums once, in a different summation order (a packed
+# kernel and the GEMM form)
+ROUTES_TOL = {torch.float16: 2e-4, torch.bfloat16: 2e-3}
+# VAE.decode against the fp32 reference: (max-abs relative to the reference's largest magnitude, rel-L2), and rel-L2 against the
+# oracle that rounds where the decoder does (test_vae_decode_against_reference states why)
+DECODE_TOL = {torch.float16: (6e-3, 5e-3), torch.bfloat16: (4e-2, 3e-2)}
+DECODE_EMU_TOL = {torch.float16: 3e-3, torch.bfloat16: 2e-2}
 
 
 @pytest.fixture(scope="module")
@@ -68,7 +75,7 @@ def test_conv3d_k3_and_residual(pkg, dtype, Cin, Cout, S, P):
         # against fp64, and within accumulation-order noise of the implicit GEMM (both round the fp32 result once)
         got_p = ops.conv3d_k3(_cl(x).to(DEV), wk, b.to(DEV), S, res=_cl(res).to(DEV), res_scale=0.5 ** 0.5, Wp=wp)
         assert rel_l2(_cf(got_p, S), (ref + res.double()) * 0.5 ** 0.5) < tol
-        assert rel_l2(got_p, got) < (2e-4 if dtype == torch.float16 else 2e-3), rel_l2(got_p, got)
+        assert rel_l2(got_p, got) < ROUTES_TOL[dtype], rel_l2(got_p, got)
         got_p = ops.conv3d_k3(_cl(x).to(DEV), wk, None, S, Wp=wp)
         assert rel_l2(_cf(got_p, S), ref - b.double().view(1, -1, 1, 1, 1)) < tol
 
@@ -123,7 +130,7 @@ def test_convtranspose_s4_with_group_statistics(pkg, dtype, P):
     gemm = ops.convtranspose_k2s2(xd, wt, b.to(DEV), S)
     got, part = ops.convtranspose_k2s2(xd, wt, b.to(DEV), S, Wp=wp, want_stats=True)
     st = ops.group_stats(part, b.to(DEV), 1e-5)
-    assert rel_l2(got, gemm) < (2e-4 if dtype == torch.float16 else 2e-3), rel_l2(got, gemm)
+    assert rel_l2(got, gemm) < ROUTES_TOL[dtype], rel_l2(got, gemm)
     ref = F.conv_transpose3d(x.double(), w.double(), b.double(), stride=2)
     assert rel_l2(_cf(got, 2 * S), ref) < (1e-3 if dtype == torch.float16 else 8e-3)
     g = got.float().cpu().view(P, 512, 32, 8).permute(0, 2, 1, 3).reshape(P, 32, -1).double()   # [P, group, voxels x 8 channels]
@@ -213,10 +220,10 @@ def test_vae_decode_against_reference(pkg, golden, dtype):
     rel_max = max_abs(out, ref) / float(ref.abs().max())
     print(f"VAE.decode {dtype}: max-abs {max_abs(out, ref):.3e} on |ref| <= {float(ref.abs().max()):.2f} (relative {rel_max:.2e}), "
           f"rel-L2 {rel_l2(out, ref):.2e}")
-    assert rel_max < (6e-3 if dtype == torch.float16 else 4e-2), rel_max
-    assert rel_l2(out, ref) < (5e-3 if dtype == torch.float16 else 3e-2), rel_l2(out, ref)
+    assert rel_max < DECODE_TOL[dtype][0], rel_max
+    assert rel_l2(out, ref) < DECODE_TOL[dtype][1], rel_l2(out, ref)
     emu = vae_ref.vae_decode(sd, z, VAE_CFG["up_channels"], VAE_CFG["layers_per_block"], emulate=dtype)
-    assert rel_l2(out, emu) < (3e-3 if dtype == torch.float16 else 2e-2)
+    assert rel_l2(out, emu) < DECODE_EMU_TOL[dtype]
     den = vae.decode(z.to(DEV), denormalize=True)
     assert rel_l2(den, vae_ref.denormalise_decoded(ref)) < (5e-3 if dtype == torch.float16 else 3e-2)
 
