@@ -694,12 +694,15 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs<DT> p) {
         } else {
             asm volatile("" ::: "memory");
             const bool k_ok = kt * BK + kc < p.K;  // zero chunk past K
+            // (ldg16 always issues its load: a chunk past K reads the row's FIRST chunk instead - with K < 64 the row's own
+            // chunk kc lies past the row, and for the last row past the operand: the encoder's 32 -> 256 shortcut, K = 32)
+            const int koff = k_ok ? kt * BK : -kc;
             if (!GATHER) {
 #pragma unroll
-                for (int i = 0; i < NA; ++i) ra[i] = ldg16<V8, S>(ga[i] + (k_ok ? kt * BK : 0), k_ok);
+                for (int i = 0; i < NA; ++i) ra[i] = ldg16<V8, S>(ga[i] + koff, k_ok);
             }
 #pragma unroll
-            for (int i = 0; i < NW; ++i) rw[i] = ldg16<V8, S>(gw[i] + (k_ok ? kt * BK : 0), k_ok);
+            for (int i = 0; i < NW; ++i) rw[i] = ldg16<V8, S>(gw[i] + koff, k_ok);
         }
     };
     auto store_tile = [&](int buf, V8 (&ra)[NA], V8 (&rw)[NW]) {

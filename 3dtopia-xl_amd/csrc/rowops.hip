@@ -750,3 +750,34 @@ extern "C" int primx_latent_denorm(const float* x, const float* mean, const floa
     PRIMX_CHECK_LAUNCH("primx_latent_denorm");
     return PRIMX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Latent normalisation + join, the inverse of primx_latent_denorm (the forward direction of inference.py:328-332):
+// out[row, c] = (v - mean[c]) / std[c] * nf with v = srt[row, c] for c < n_srt and z[row, c - n_srt] behind it.
+__global__ void latent_norm_kernel(const float* __restrict__ srt, const float* __restrict__ z, const float* __restrict__ mean,
+                                   const float* __restrict__ stdv, float nf, float* __restrict__ out, int64_t rows, int C,
+                                   int n_srt) {
+#pragma clang fp contract(off)
+    const int64_t total = rows * C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / C;
+        const int c = (int)(i - r * C);
+        const float v = c < n_srt ? srt[r * n_srt + c] : z[r * (C - n_srt) + (c - n_srt)];
+        const float d = v - mean[c];
+        const float q = d / stdv[c];
+        out[i] = q * nf;
+    }
+}
+
+extern "C" int primx_latent_norm(const float* srt, const float* z, const float* mean, const float* stdv, float nf, float* out,
+                                 int64_t rows, int C, int n_srt, void* stream) {
+    PRIMX_REQUIRE(srt && z && mean && stdv && out, "primx_latent_norm: null pointer");
+    PRIMX_REQUIRE(rows > 0 && C > n_srt && n_srt > 0, "primx_latent_norm: bad shape");
+    const int64_t total = rows * C;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(latent_norm_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, srt, z, mean, stdv, nf, out, rows, C,
+                       n_srt);
+    PRIMX_CHECK_LAUNCH("primx_latent_norm");
+    return PRIMX_OK;
+}

@@ -850,6 +850,60 @@ def latent_denorm(x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, nf: fl
     return srt, z
 
 
+def latent_norm(srt: torch.Tensor, z: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, nf: float) -> torch.Tensor:
+    """The inverse of latent_denorm: (srt [..., n_srt], z [..., C - n_srt]) fp32 -> [..., C] = (v - mean) / std * nf."""
+    n_srt, C = srt.shape[-1], srt.shape[-1] + z.shape[-1]
+    rows = srt.numel() // n_srt
+    if tuple(srt.shape[:-1]) != tuple(z.shape[:-1]) or mean.numel() != C or std.numel() != C:
+        raise RuntimeError("latent_norm: srt / z must share their leading dimensions; mean / std hold one entry per channel")
+    out = torch.empty(*srt.shape[:-1], C, dtype=torch.float32, device=srt.device)
+    check(_lib.load().primx_latent_norm(_dev(srt, "srt", torch.float32), _dev(z, "z", torch.float32),
+                                        _dev(mean, "mean", torch.float32), _dev(std, "std", torch.float32), float(nf),
+                                        out.data_ptr(), rows, C, n_srt, _stream()), "primx_latent_norm")
+    return out
+
+
+# ----------------------------------------------------------------------------- VAE encoder (csrc/vaeenc.hip)
+def enc_conv_in(x: torch.Tensor, Wk: torch.Tensor, bias: torch.Tensor, normalize: bool = False) -> torch.Tensor:
+    """x: [P, 6, 8, 8, 8] fp32 channel-first; Wk: [32, Kpad] 16-bit (k = tap*6 + ci); bias [32] -> [P, 512, 32] channels-last
+    of Wk's dtype.  normalize: channel 0 * 5, the others * 2 - 1 before the rounding to 16 bits."""
+    P = x.shape[0]
+    if tuple(x.shape[1:]) != (6, 8, 8, 8) or Wk.shape[0] != 32 or Wk.shape[1] < 162 or bias.numel() != 32:
+        raise ValueError("enc_conv_in: x must be [P, 6, 8, 8, 8], Wk [32, >= 162], bias [32]")
+    out = torch.empty(P, 512, 32, dtype=Wk.dtype, device=x.device)
+    _timed(f"enc_conv_in_kernel<{dtype_code(Wk.dtype)}> 6->32 @8^3 x{P}", 2.0 * P * 512 * 32 * 162, lambda: check(
+        _lib.load().primx_enc_conv_in(_dev(x, "x", torch.float32), _dev(Wk, "Wk"), Wk.shape[1], _dev(bias, "bias", Wk.dtype),
+                                      out.data_ptr(), P, int(normalize), dtype_code(Wk.dtype), _stream()), "primx_enc_conv_in"))
+    return out
+
+
+def conv3d_down(x: torch.Tensor, Wp: PackedConv3, bias: torch.Tensor) -> torch.Tensor:
+    """x: [P, 512, 32] 16-bit -> [P, 64, 32]: Conv3d(32 -> 32, k3, stride 2, pad 1) on the 8^3 grid; Wp: the "s8c32" image
+    of the [32, 864] weight (pack_conv3)."""
+    P, V, Cin = x.shape
+    if not (Wp.kind == "s8c32" and Wp.Cout == 32 and V == 512 and Cin == 32) or bias.numel() != 32:
+        raise ValueError("conv3d_down: needs [P, 512, 32] activations, the 32 -> 32 s8c32 image and a bias of 32")
+    out = torch.empty(P, 64, 32, dtype=x.dtype, device=x.device)
+    _timed(f"conv3_down_kernel<{dtype_code(x.dtype)}> 32->32 @8^3/2 x{P}", 2.0 * P * 64 * 32 * 864, lambda: check(
+        _lib.load().primx_conv3d_down_s8c32(_dev(x, "x"), _dev(Wp.Wp, "Wp", x.dtype), _dev(bias, "bias", x.dtype), out.data_ptr(),
+                                            P, dtype_code(x.dtype), _stream()), "primx_conv3d_down_s8c32"))
+    return out
+
+
+def enc_head(x: torch.Tensor, Wk: torch.Tensor, bias: torch.Tensor, qw: torch.Tensor, qb: torch.Tensor) -> torch.Tensor:
+    """x: [P, 64, 256] 16-bit (norm_out + SiLU); Wk: [2, Kpad >= 6912] 16-bit conv_out weight (k = tap*256 + ci); bias fp32 [2];
+    qw fp32 [2, 2], qb fp32 [2] (quant_conv) -> fp32 [P, 2, 4, 4, 4], the posterior's parameters."""
+    P, V, Cin = x.shape
+    if (V, Cin) != (64, 256) or Wk.shape[0] != 2 or Wk.shape[1] < 6912 or bias.numel() != 2 or qw.numel() != 4 or qb.numel() != 2:
+        raise ValueError("enc_head: needs [P, 64, 256] activations, Wk [2, >= 6912], bias [2], qw [2, 2], qb [2]")
+    out = torch.empty(P, 2, 4, 4, 4, dtype=torch.float32, device=x.device)
+    _timed(f"enc_head_kernel<{dtype_code(x.dtype)}> 256->2->2 @4^3 x{P}", 2.0 * P * 64 * 2 * 6912, lambda: check(
+        _lib.load().primx_enc_head(_dev(x, "x"), _dev(Wk, "Wk", x.dtype), Wk.shape[1], _dev(bias, "bias", torch.float32),
+                                   _dev(qw, "qw", torch.float32), _dev(qb, "qb", torch.float32), out.data_ptr(), P,
+                                   dtype_code(x.dtype), _stream()), "primx_enc_head"))
+    return out
+
+
 # ----------------------------------------------------------------------------- DINOv2 conditioner pieces
 def vit_tokens(patches: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, reg: Optional[torch.Tensor]) -> torch.Tensor:
     """patches [B, np, D], cls [D], pos [1+np, D], reg [R, D] or None (all fp32) -> tokens [B, 1+R+np, D] fp32

@@ -68,6 +68,40 @@ def latents_to_primitives(samples: torch.Tensor, vae, latent_mean: Optional[Sequ
     return torch.cat([srt, feat], dim=-1)
 
 
+@ops.on_input_device
+def primitives_to_latents(recon_param: torch.Tensor, vae, latent_mean: Optional[Sequence[float]] = None,
+                          latent_std: Optional[Sequence[float]] = None, latent_nf: float = 1.0, sample: bool = False,
+                          generator=None, max_prims_per_call: int = 8 * 2048) -> torch.Tensor:
+    """recon_param (B, N_prim, 4 + 6 * 8^3) fp32 -> (B, N_prim, 68) fp32 tokens in the DiT's normalised space: the inverse of
+    latents_to_primitives.  The payload goes through ``vae.encode(normalize=True)`` in chunks of max_prims_per_call
+    primitives; the posterior's mode (``sample=True``: a sample, its noise drawn once with ``generator`` for all B * N primitives,
+    so it does not depend on the chunking) and the srt columns are normalised
+    with the per-channel statistics and joined by one kernel (primx_latent_norm)."""
+    if not recon_param.is_cuda:
+        raise RuntimeError("primitives_to_latents needs HIP device tensors; there is no CPU path")
+    B, N, C = recon_param.shape
+    if latent_mean is None:
+        raise NotImplementedError("per-channel latent_mean / latent_std are required (configs/inference_dit.yml:64-65)")
+    S2 = round(((C - 4) / 6) ** (1.0 / 3.0))
+    if 6 * S2 ** 3 != C - 4:
+        raise AssertionError("recon_param must have 4 + 6 * (2S)^3 channels")
+    mean, std = _latent_stats(latent_mean, latent_std, recon_param.device)
+    rp = recon_param.float().reshape(B * N, C)
+    zs, noise = [], None
+    for lo in range(0, B * N, max_prims_per_call):
+        post = vae.encode(rp[lo:lo + max_prims_per_call, 4:].reshape(-1, 6, S2, S2, S2), normalize=True)
+        z = post.mode()
+        if sample:
+            if noise is None:      # one draw for all B * N primitives: a sample does not depend on max_prims_per_call
+                noise = torch.randn((B * N,) + tuple(z.shape[1:]), device=z.device, dtype=z.dtype, generator=generator)
+            z = post.mean + post.std * noise[lo:lo + z.shape[0]]
+        zs.append(z.reshape(z.shape[0], -1))
+    z = (zs[0] if len(zs) == 1 else torch.cat(zs, dim=0)).contiguous()
+    if mean.numel() != 4 + z.shape[1] or std.numel() != mean.numel():
+        raise AssertionError("latent_mean / latent_std must have one entry per latent channel")
+    return ops.latent_norm(rp[:, :4].contiguous(), z, mean, std, latent_nf).view(B, N, -1)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # On-disk formats of the hot path (SURVEY.md section 8f, N4): the two checkpoints the CLI loads and the `denoised.pt`
 # it writes between sampling and mesh extraction.

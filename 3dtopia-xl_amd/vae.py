@@ -1,9 +1,8 @@
-"""PrimX 3D-VAE with the decode half on the HIP path - drop-in for ``models.vae3d_dib.VAE``.
+"""PrimX 3D-VAE on the HIP path - drop-in for ``models.vae3d_dib.VAE``.
 
 Same constructor kwargs and the same ``state_dict`` keys as the reference (models/vae3d_dib.py:389-453),
 including the encoder and ``quant_conv`` tensors that inference never touches (checkpoints are loaded
-strictly, inference.py:257-258).  Only ``decode`` computes; ``encode``/``forward`` are training-side
-and raise.
+strictly, inference.py:257-258).  ``decode``, ``encode`` and ``forward`` compute (inference only: no backward).
 
 Decoder data layout (MI355X-first): activations are channels-LAST 16-bit ``[P, V, C]`` (P primitives,
 V = S^3 voxels in z,y,x raster order), so every 3x3x3 convolution is an implicit GEMM on MFMA whose A
@@ -14,6 +13,10 @@ GroupNorm statistics stay fp32.  The reference runs this decoder in fp32 (TF32 c
 the CLI's allow_tf32 flags, inference.py:377-380); here the storage/MFMA-input type is
 ``compute_dtype`` (fp16 by default: 10 mantissa bits, the same input precision as TF32) with fp32
 accumulation - the tolerance is stated in tests/test_hip_vae.py and DESIGN.md.
+
+The encoder (``encode``) keeps the same layout and rounding points.  Its 32-channel ResnetBlocks on the 8^3 grid, the
+256-channel ones on the 4^3 grid and the mid block run on the decoder's kernels; conv_in (6 -> 32 from the fp32
+channel-first payload), the stride-2 downsample and conv_out + quant_conv have kernels of their own (csrc/vaeenc.hip).
 """
 from __future__ import annotations
 
@@ -96,8 +99,45 @@ class UpBlock(nn.Module):
         self.upsample = nn.ConvTranspose3d(out_channels, out_channels, kernel_size=2, stride=2) if upsample else None
 
 
+class DiagonalGaussianDistribution:
+    """The posterior ``VAE.encode`` returns (vae3d_dib.py:50-90): plain torch on the small [P, 2C, ...] parameter tensor.
+    ``sample`` takes an optional generator (the reference draws from the default one)."""
+
+    def __init__(self, parameters: torch.Tensor, deterministic: bool = False):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+        if self.deterministic:
+            self.var = self.std = torch.zeros_like(self.mean, device=self.parameters.device, dtype=self.parameters.dtype)
+
+    def sample(self, generator=None):
+        noise = torch.randn(self.mean.shape, device=self.parameters.device, dtype=self.parameters.dtype, generator=generator)
+        return self.mean + self.std * noise
+
+    def kl(self, other=None, dims=(1, 2, 3, 4)):
+        dims = list(dims)
+        if self.deterministic:
+            return torch.Tensor([0.0])
+        if other is None:
+            return 0.5 * torch.mean(torch.pow(self.mean, 2) + self.var - 1.0 - self.logvar, dim=dims)
+        return 0.5 * torch.mean(torch.pow(self.mean - other.mean, 2) / other.var + self.var / other.var - 1.0 - self.logvar
+                                + other.logvar, dim=dims)
+
+    def nll(self, sample, dims=(1, 2, 3, 4)):
+        if self.deterministic:
+            return torch.Tensor([0.0])
+        logtwopi = np.log(2.0 * np.pi)
+        return 0.5 * torch.sum(logtwopi + self.logvar + torch.pow(sample - self.mean, 2) / self.var, dim=list(dims))
+
+    def mode(self):
+        return self.mean
+
+
 class Encoder(nn.Module):
-    """Training-side half: holds the checkpoint's tensors, never runs (vae3d_dib.py:270-327)."""
+    """conv_in -> DownBlocks -> MidBlock -> GN/SiLU/conv_out (vae3d_dib.py:270-327); run by ``VAE.encode``."""
 
     def __init__(self, in_channels=1, out_channels=32, down_channels=(8, 16, 32, 64), mid_attention=True,
                  layers_per_block=2, skip_scale=np.sqrt(0.5), gradient_checkpointing=False):
@@ -160,13 +200,16 @@ class VAE(nn.Module):
         self.post_quant_conv = nn.Conv3d(latent_channels, latent_channels, 1)
         self.compute_dtype = torch.float16
         self._pack: Dict = {}
+        self._enc_pack: Dict = {}
 
     # ------------------------------------------------------------------ packing
     def repack(self) -> None:
         self._pack = {}
+        self._enc_pack = {}
 
     def _apply(self, fn, *a, **k):
         self.__dict__["_pack"] = {}
+        self.__dict__["_enc_pack"] = {}
         self.__dict__["_attn_ws"] = {}
         return super()._apply(fn, *a, **k)
 
@@ -348,8 +391,85 @@ class VAE(nn.Module):
             out = ops.vae_output(h, denormalize)
         return out.view(P, -1, S, S, S)
 
-    def encode(self, x):
-        raise NotImplementedError("the encoder is training-only and outside the accelerated path")
+    # ------------------------------------------------------------------ encode
+    _ENC_SHIPPED = "in_channels=6, down_channels=[32, 256], latent_channels=1 on 8^3 inputs (the shipped PrimX VAE)"
 
-    def forward(self, x, sample=True):
-        raise NotImplementedError("VAE.forward (encode + decode) is training-only; use decode()")
+    def packed_encoder(self, dt: torch.dtype) -> Dict:
+        """16-bit / packed copies of the encoder's weights, made on the first encode (per dtype and device)."""
+        key = (dt, self.quant_conv.weight.device)
+        if key in self._enc_pack:
+            return self._enc_pack[key]
+        enc = self.encoder
+        chans = [b.nets[0].out_channels for b in enc.down_blocks]
+        if enc.conv_in.in_channels != 6 or chans != [32, 256] or self.latent_channels != 1:
+            raise NotImplementedError(f"the accelerated encoder covers {self._ENC_SHIPPED}; got in_channels="
+                                      f"{enc.conv_in.in_channels}, down_channels={chans}, latent_channels={self.latent_channels}")
+        c16 = lambda t: t.detach().to(dt).contiguous()
+        f32 = lambda t: t.detach().float().contiguous()
+        with torch.no_grad():
+            pk = {
+                "w_in": _conv_weight_as_gemm(enc.conv_in.weight.detach(), dt), "c_in": c16(enc.conv_in.bias),
+                "down": [],
+                "mid": [self._res_pack(n, dt) for n in enc.mid_block.nets],
+                "attn": [],
+                "g_out": f32(enc.norm_out.weight), "b_out": f32(enc.norm_out.bias), "groups_out": enc.norm_out.num_groups,
+                "eps_out": enc.norm_out.eps,
+                # conv_out's accumulation and quant_conv stay fp32 (csrc/vaeenc.hip enc_head_kernel): the weight and bias of
+                # conv_out are the 16-bit values, quant_conv's 2 x 2 weight and bias are used as they are
+                "w_out": _conv_weight_as_gemm(enc.conv_out.weight.detach(), dt), "c_out": f32(c16(enc.conv_out.bias)),
+                "qw": f32(self.quant_conv.weight.reshape(2, 2)), "qb": f32(self.quant_conv.bias),
+            }
+            for db in enc.down_blocks:
+                d = {"nets": [self._res_pack(n, dt) for n in db.nets], "w_down": None, "c_down": None}
+                if db.downsample is not None:
+                    d["w_down"] = ops.pack_conv3(_conv_weight_as_gemm(db.downsample.weight.detach(), dt), db.downsample.in_channels)
+                    d["c_down"] = c16(db.downsample.bias)
+                    if d["w_down"] is None:
+                        raise RuntimeError("VAE.encode: the stride-2 kernel needs the packed weight image (PRIMX_CONV_REG=0 disables it)")
+                pk["down"].append(d)
+            for a in enc.mid_block.attns:
+                pk["attn"].append(None if a is None else {
+                    "g": f32(a.norm.weight), "b": f32(a.norm.bias), "groups": a.norm.num_groups, "eps": a.norm.eps,
+                    "w_qkv": c16(a.attn.qkv.weight), "b_qkv": None if a.attn.qkv.bias is None else c16(a.attn.qkv.bias),
+                    "w_proj": c16(a.attn.proj.weight),
+                    "b_proj": None if a.attn.proj.bias is None else c16(a.attn.proj.bias),
+                    "heads": a.attn.num_heads, "residual": a.residual,
+                })
+        self._enc_pack = {key: pk}
+        return pk
+
+    @ops.on_input_device
+    def encode(self, x: torch.Tensor, normalize: bool = False) -> DiagonalGaussianDistribution:
+        """x: (P, 6, 8, 8, 8) fp32 primitive payloads -> the posterior over (P, 1, 4, 4, 4) latents (vae3d_dib.py:431-435).
+
+        ``normalize=True`` first applies the inverse of ``decode(..., denormalize=True)`` (channel 0 * 5, the others
+        * 2 - 1) inside the input kernel, so a ``recon_param`` payload can be passed as it is."""
+        if not x.is_cuda:
+            raise RuntimeError("VAE.encode needs HIP device tensors; there is no CPU path")
+        if x.dim() != 5 or tuple(x.shape[1:]) != (6, 8, 8, 8):
+            raise NotImplementedError(f"the accelerated encoder covers {self._ENC_SHIPPED}; got an input of shape {tuple(x.shape)}")
+        dt = self.compute_dtype
+        pk = self.packed_encoder(dt)
+        with torch.no_grad():
+            S = 8
+            h = ops.enc_conv_in(x.float().contiguous(), pk["w_in"], pk["c_in"], normalize)
+            for d in pk["down"]:
+                for rw in d["nets"]:
+                    h = self._resnet(h, rw, S)
+                if d["w_down"] is not None:
+                    h = ops.conv3d_down(h, d["w_down"], d["c_down"])
+                    S //= 2
+            h = self._resnet(h, pk["mid"][0], S)
+            for aw, rw in zip(pk["attn"], pk["mid"][1:]):
+                if aw is not None:
+                    h = self._attention(h, aw)
+                h = self._resnet(h, rw, S)
+            h = ops.groupnorm_silu(h, pk["g_out"], pk["b_out"], pk["groups_out"], pk["eps_out"], True)
+            params = ops.enc_head(h, pk["w_out"], pk["c_out"], pk["qw"], pk["qb"])
+        return DiagonalGaussianDistribution(params)
+
+    def forward(self, x: torch.Tensor, sample: bool = True, generator=None) -> Tuple[torch.Tensor, DiagonalGaussianDistribution]:
+        """(decode(z), posterior) with z a sample of, or the mode of, encode(x) (vae3d_dib.py:442-454)."""
+        p = self.encode(x)
+        z = p.sample(generator) if sample else p.mode()
+        return self.decode(z), p

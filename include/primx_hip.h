@@ -51,14 +51,15 @@
  *     has a [P, 512, 256] activation of exactly 2^31 elements - and the kernels form them in 64 bits:
  *       * the VAE decoder family (primx_groupnorm_silu, primx_conv_in, primx_conv3d_k3, primx_conv3d_s4_packed,
  *         primx_conv3d_s8_packed, primx_conv3d_s8_fused, primx_conv3d_s8c32_packed, primx_convtranspose_k2s2,
- *         primx_convtranspose_s4_packed, primx_vae_output): primitive * V * C, and the `part` statistics per primitive;
+ *         primx_convtranspose_s4_packed, primx_vae_output) and the encoder's three kernels (primx_enc_conv_in,
+ *         primx_conv3d_down_s8c32, primx_enc_head): primitive * V * C, and the `part` statistics per primitive;
  *       * the GEMM family (primx_linear, _residual, _gate_residual[_ln], _heads and the fold forms): row * K, row * N and the
  *         head-layout offsets of every epilogue.  One kernel keeps 32-bit BYTE offsets: the 128-byte ring of the 256 x 288
  *         tile; the dispatch takes it only while M * K < 2^31 and N * K < 2^31 and falls back to the 64-byte ring (64-bit
  *         offsets, same results to the contract) from there on - a choice of kernel, not a limit of the entry point;
  *       * primx_attention with the compact 64-token operands: (batch * H + head) * 64 * DP;
- *       * the elementwise kernels (primx_cast16, primx_silu_cast, primx_silu_f32, primx_cfg_combine, primx_latent_denorm):
- *         a 64-bit grid-stride index.
+ *       * the elementwise kernels (primx_cast16, primx_silu_cast, primx_silu_f32, primx_cfg_combine, primx_latent_denorm,
+ *         primx_latent_norm): a 64-bit grid-stride index.
  *   - REFUSED with PRIMX_EINVAL before any launch, because the kernel's flat index is an `int`: primx_timestep_embedding with
  *     B * (dim / 2) >= 2^31 and primx_point_features with 3 * T * F >= 2^31 (thousands of times the shipped sizes).  The mesh
  *     entry points state their own limits (3 nx ny nz, 3 V, 9 F, 6 V < 2^31) where they are declared.
@@ -79,7 +80,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 30
+#define PRIMX_ABI_VERSION 31
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -529,6 +530,35 @@ int primx_vae_output(const void* in, float* out, int P, int V, int C, int denorm
  * Replaces inference.py:328-332 / app.py:119-123. */
 int primx_latent_denorm(const float* x, const float* mean, const float* stdv, float nf, float* srt, float* z,
                         int64_t rows, int C, int n_srt, void* stream);
+
+/* The inverse of primx_latent_denorm: out[row, c] = (v - mean[c]) / std[c] * nf (each op rounded to fp32, as torch does),
+ * v = srt[row, c] for c < n_srt, z[row, c - n_srt] behind it; out [rows, C].  ABI 31. */
+int primx_latent_norm(const float* srt, const float* z, const float* mean, const float* stdv, float nf, float* out,
+                      int64_t rows, int C, int n_srt, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * VAE encoder (models/vae3d_dib.py:270-327, 431-435), shipped configuration: in_channels 6, down_channels [32, 256],
+ * latent_channels 1.  ABI 31.  Everything between these three kernels runs on the decoder's entry points above
+ * (csrc/vaeenc.hip).
+ * -------------------------------------------------------------------------------------------- */
+
+/* Encoder.conv_in: Conv3d(6 -> 32, k3, p1) on the 8^3 grid.  in: fp32 channel-first [P, 6, 8, 8, 8] (the layout of
+ * primx_vae_output); Wk: 16-bit [32, Kpad], k = tap * 6 + ci (the form of primx_conv3d_k3, Kpad >= 162); bias 16-bit [32];
+ * out: 16-bit channels-last [P, 512, 32].  normalize != 0 first maps channel 0 to x * 5 and the others to x * 2 - 1 (the
+ * inverse of inference.py:345-346); the (normalised) input is rounded to 16 bits, then zero-padded. */
+int primx_enc_conv_in(const float* in, const void* Wk, int Kpad, const void* bias, void* out, int P, int normalize, int dtype,
+                      void* stream);
+
+/* DownBlock.downsample: Conv3d(32 -> 32, k3, s2, p1), [P, 512, 32] -> [P, 64, 32] (vae3d_dib.py:168,181-182): output voxel o
+ * reads inputs 2 o - 1 .. 2 o + 1.  Wp: the 27 * 32 * 32 image primx_conv3d_s8c32_pack makes for Cout = 32. */
+int primx_conv3d_down_s8c32(const void* in, const void* Wp, const void* bias, void* out, int P, int dtype, void* stream);
+
+/* Encoder.conv_out (256 -> 2, k3, p1, 4^3 grid) + quant_conv (2 -> 2, 1x1x1) (vae3d_dib.py:307,325,428,433).  in: the
+ * 16-bit GroupNorm + SiLU output [P, 64, 256]; Wk: 16-bit [2, Kpad], k = tap * 256 + ci, Kpad >= 6912; bias fp32 [2]
+ * (conv_out's); qw fp32 [2, 2], qb fp32 [2] (quant_conv's, unrounded); out fp32 [P, 2, 4, 4, 4] = the posterior's
+ * `parameters`.  fp32 accumulation, nothing is rounded to 16 bits. */
+int primx_enc_head(const void* in, const void* Wk, int Kpad, const float* bias, const float* qw, const float* qb, float* out,
+                   int P, int dtype, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * PrimSDF field query (models/primsdf.py:52-109; inference.py:106-116, 180-193)
