@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PRIMX_LIB") or os.path.join(_HERE, "csrc", "libprimx_
 F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF = 0, 1, 2
 HEADS_ROWS, HEADS_VT, HEADS_KROWS = 0, 1, 2
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 _p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
@@ -80,6 +80,9 @@ SIGNATURES = {
     "primx_pack_heads": [_p, _l, _l, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "primx_cfg_combine": [_p, _p, _i, _l, _f, _p],
     "primx_diffusion_step": [_p, _p, _i, _l, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
+    "primx_q_sample": [_p, _p, _l, _p, _i, _p, _p],
+    "primx_diffusion_reverse_step": [_p, _p, _i, _l, _i, _i, _p, _i, _i, _i, _p, _p, _p],
+    "primx_diffusion_step_keep": [_p, _p, _i, _l, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p],
     "primx_groupnorm_silu": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _i, _p],
     "primx_conv3d_k3": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p],
     "primx_conv3d_s4_pack": [_p, _p, _i, _i, _p],
@@ -145,7 +148,8 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # 29 added the mesh-cleanup entry points (_MESHCLEAN_ENTRY_POINTS: a version-28 build serves everything but mesh.clean_mesh);
 # version 30 added the mesh-decimation entry points (_MESHDECIM_ENTRY_POINTS: a version-29 build serves everything but
 # mesh.decimate_mesh); version 31 added the VAE encoder's entry points (_VAEENC_ENTRY_POINTS: a version-30 build serves everything
-# but VAE.encode / VAE.forward and pipeline.primitives_to_latents)
+# but VAE.encode / VAE.forward and pipeline.primitives_to_latents); version 32 added the editing entry points (_EDIT_ENTRY_POINTS:
+# a version-31 build serves everything but q_sample, ddim_reverse_sample and the kept-token DDIM loops)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
@@ -158,7 +162,8 @@ _MESHDECIM_ENTRY_POINTS: set = {"primx_meshdecim_workspace", "primx_meshdecim_ed
                                 "primx_meshdecim_costs", "primx_meshdecim_select", "primx_meshdecim_collapse",
                                 "primx_meshdecim_finish", "primx_meshdecim_normals"}
 _VAEENC_ENTRY_POINTS: set = {"primx_latent_norm", "primx_enc_conv_in", "primx_conv3d_down_s8c32", "primx_enc_head"}
-_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30)
+_EDIT_ENTRY_POINTS: set = {"primx_q_sample", "primx_diffusion_reverse_step", "primx_diffusion_step_keep"}
+_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31)
 _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
@@ -221,6 +226,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         if got < 30 and name in _MESHDECIM_ENTRY_POINTS:
             continue
         if got < 31 and name in _VAEENC_ENTRY_POINTS:
+            continue
+        if got < 32 and name in _EDIT_ENTRY_POINTS:
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes

@@ -634,6 +634,56 @@ def diffusion_step(x: torch.Tensor, model_out: torch.Tensor, coef: torch.Tensor,
     return sample, x0
 
 
+def q_sample(x_start: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor, step: int) -> torch.Tensor:
+    """coef[step][0] * x_start + coef[step][1] * noise (gaussian_diffusion.py:216-231): fp32, any shape."""
+    if x_start.shape != noise.shape:
+        raise RuntimeError("q_sample: noise must have x_start's shape")
+    out = torch.empty_like(x_start)
+    check(_lib.load().primx_q_sample(_dev(x_start, "x_start", torch.float32), _dev(noise, "noise", torch.float32), x_start.numel(),
+                                     _dev(coef, "coef", torch.float32), step, out.data_ptr(), _stream()), "primx_q_sample")
+    return out
+
+
+def diffusion_reverse_step(x: torch.Tensor, model_out: torch.Tensor, coef: torch.Tensor, step: int, *, mean_type: int,
+                           clip_denoised: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ddim_reverse_sample (gaussian_diffusion.py:580-616): level `step` -> (level `step + 1`, pred_xstart)."""
+    B, nt, Cc = x.shape
+    model_out = model_out.contiguous()
+    sample = torch.empty_like(x)
+    x0 = torch.empty_like(x)
+    check(_lib.load().primx_diffusion_reverse_step(
+        _dev(x, "x", torch.float32), _dev(model_out, "model_out"), dtype_code(model_out.dtype), B * nt, Cc,
+        model_out.shape[-1], _dev(coef, "coef", torch.float32), step, mean_type, int(clip_denoised),
+        sample.data_ptr(), x0.data_ptr(), _stream()), "primx_diffusion_reverse_step")
+    return sample, x0
+
+
+def diffusion_step_keep(x: torch.Tensor, model_out: torch.Tensor, coef: torch.Tensor, step: int, *, mean_type: int,
+                        var_type: int, ancestral: bool, clip_denoised: bool, noise: Optional[torch.Tensor],
+                        known: torch.Tensor, known_noise: torch.Tensor, keep: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """diffusion_step with the elements flagged by `keep` (uint8 [B, n_tok]: whole rows, or [B, n_tok, C]) held on the known
+    trajectory: pred_xstart = known, sample = q_sample(known, known_noise, step - 1) (`known` at step 0)."""
+    B, nt, Cc = x.shape
+    if known.shape != x.shape or known_noise.shape != x.shape:
+        raise RuntimeError("diffusion_step_keep: known / known_noise must have x's shape")
+    if tuple(keep.shape) == (B, nt):
+        keep_stride = 1
+    elif tuple(keep.shape) == (B, nt, Cc):
+        keep_stride = Cc
+    else:
+        raise RuntimeError(f"diffusion_step_keep: keep must be [B, n_tok] or [B, n_tok, C], got {tuple(keep.shape)}")
+    model_out = model_out.contiguous()
+    sample = torch.empty_like(x)
+    x0 = torch.empty_like(x)
+    check(_lib.load().primx_diffusion_step_keep(
+        _dev(x, "x", torch.float32), _dev(model_out, "model_out"), dtype_code(model_out.dtype), B * nt, Cc,
+        model_out.shape[-1], _dev(coef, "coef", torch.float32), step, mean_type, var_type, int(ancestral),
+        int(clip_denoised), _dev(noise, "noise", torch.float32) if noise is not None else None,
+        _dev(known, "known", torch.float32), _dev(known_noise, "known_noise", torch.float32), _dev(keep, "keep", torch.uint8),
+        keep_stride, sample.data_ptr(), x0.data_ptr(), _stream()), "primx_diffusion_step_keep")
+    return sample, x0
+
+
 # ----------------------------------------------------------------------------- VAE decoder
 def groupnorm_silu(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float,
                    silu: bool) -> torch.Tensor:

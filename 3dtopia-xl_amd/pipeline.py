@@ -1,4 +1,5 @@
-"""Post-sampling driver of the hot path: denoised latents -> per-primitive PBR voxel payload.
+"""Post-sampling driver of the hot path: denoised latents -> per-primitive PBR voxel payload, and back (`primitives_to_latents`,
+`redenoise_primitives`: edit a stored asset and re-denoise it).
 
 Mirrors what the reference's CLI / app do between the sampler and the ray-marcher / mesh export
 (inference.py:326-348, app.py:117-139):  de-normalise with the per-channel latent statistics, split
@@ -100,6 +101,61 @@ def primitives_to_latents(recon_param: torch.Tensor, vae, latent_mean: Optional[
     if mean.numel() != 4 + z.shape[1] or std.numel() != mean.numel():
         raise AssertionError("latent_mean / latent_std must have one entry per latent channel")
     return ops.latent_norm(rp[:, :4].contiguous(), z, mean, std, latent_nf).view(B, N, -1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Editing a stored asset: encode -> noise or invert to a level -> re-denoise from there, with part
+# of the tokens optionally held -> decode.  DESIGN.md "Editing" has the level convention and the kept-token contract.
+def keep_mask(n_prim_mask: torch.Tensor, channels: str = "all", n_channels: int = 68) -> torch.Tensor:
+    """A per-primitive bool mask (B, N) -> the (B, N, n_channels) element mask `redenoise_primitives(keep=...)` and
+    `ddim_sample_loop(keep=...)` take: of the flagged primitives keep every channel ("all"), only scale + xyz ("srt",
+    channels 0..3: keep the layout, regenerate the appearance) or only the appearance latents ("latent", channels 4..)."""
+    if n_prim_mask.dtype != torch.bool or n_prim_mask.dim() != 2:
+        raise ValueError("n_prim_mask must be a bool tensor of shape (B, N_prim)")
+    if channels not in ("all", "srt", "latent"):
+        raise ValueError(f'channels must be "all", "srt" or "latent", got {channels!r}')
+    ch = torch.zeros(n_channels, dtype=torch.bool, device=n_prim_mask.device)
+    ch[{"all": slice(None), "srt": slice(0, 4), "latent": slice(4, None)}[channels]] = True
+    return n_prim_mask[:, :, None] & ch
+
+
+def redenoise_primitives(recon_param: torch.Tensor, vae, model, diffusion, y: torch.Tensor, *, start_step: int,
+                         mode: str = "noise", keep: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                         generator=None, cfg_scale: float = 6.0, invert_cfg_scale: float = 1.0,
+                         precision_dtype: torch.dtype = torch.float16, enable_amp: bool = True,
+                         latent_mean: Optional[Sequence[float]] = None, latent_std: Optional[Sequence[float]] = None,
+                         latent_nf: float = 1.0) -> torch.Tensor:
+    """recon_param (B, N_prim, 4 + 6 * 8^3) -> recon_param of the edited asset: `primitives_to_latents`, then the tokens are
+    taken to level `start_step` of `diffusion` - mode "noise": `q_sample` with `noise` (drawn once with `generator` when None);
+    mode "invert": `ddim_reverse_sample_loop(stop_step=start_step)` under `model.forward_with_cfg` at `invert_cfg_scale` - and
+    `ddim_sample_loop(start_step=start_step)` re-denoises them under the conditioning `y` at `cfg_scale`; `latents_to_primitives`
+    decodes.  `keep` (bool; (B, N_prim) keeps whole primitives, (B, N_prim, 68) elements, see `keep_mask`) holds those tokens
+    on the input asset's own trajectory: they come out as the encode -> decode round trip of the input, bit for bit.  `keep`
+    needs mode "noise": the kept rows of an inversion would need the inversion's own implied noise."""
+    if mode not in ("noise", "invert"):
+        raise ValueError(f'mode must be "noise" or "invert", got {mode!r}')
+    if keep is not None and mode == "invert":
+        raise ValueError('keep needs mode="noise": an inverted trajectory has no noise tensor to hold the kept tokens on')
+    if not (0 <= int(start_step) < diffusion.num_timesteps):
+        raise ValueError(f"start_step must lie in 0 .. {diffusion.num_timesteps - 1}, got {start_step}")
+    start_step = int(start_step)
+    tokens = primitives_to_latents(recon_param, vae, latent_mean, latent_std, latent_nf)
+    with ops.device_of(tokens):
+        kw = dict(y=y, cfg_scale=cfg_scale, precision_dtype=precision_dtype, enable_amp=enable_amp)
+        if mode == "noise":
+            if noise is None:
+                noise = torch.randn(tokens.shape, device=tokens.device, dtype=torch.float32, generator=generator)
+            t = torch.full((tokens.shape[0],), start_step, dtype=torch.int64, device=tokens.device)
+            level = diffusion.q_sample(tokens, t, noise)
+        elif start_step == 0:
+            level = tokens                      # level 0 is what the inversion starts from
+        else:
+            level = diffusion.ddim_reverse_sample_loop(model.forward_with_cfg, tokens, clip_denoised=False,
+                                                       model_kwargs=dict(kw, cfg_scale=invert_cfg_scale), stop_step=start_step)
+        held = {} if keep is None else dict(known=tokens, keep=keep, known_noise=noise)
+        samples = diffusion.ddim_sample_loop(model.forward_with_cfg, tuple(tokens.shape), noise=level, clip_denoised=False,
+                                             model_kwargs=kw, start_step=start_step, **held)
+    return latents_to_primitives(samples, vae, latent_mean, latent_std, latent_nf)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
