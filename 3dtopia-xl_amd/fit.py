@@ -1,0 +1,231 @@
+"""Fit PrimX primitives to a mesh on MI355X - SURVEY.md section 8(f) row N7.
+
+The reference never released this step: `PrimSDF._init_param` is an empty `pass` (models/primsdf.py:48-50).  What is built
+here is the initialisation the 3DTopia-XL paper describes: sample candidate points uniformly on the surface, farthest-point-
+sample N of them as primitive centres, set each scale to the distance to the nearest other centre, and fill each primitive's
+S^3 payload with the mesh's signed distance, colour and material at `t_k + s_k * I`.  The short gradient refinement the paper
+runs afterwards is NOT built.
+
+Kernels (csrc/meshfield.hip, rules in include/primx_hip.h "Primitive fitting"): `primx_mesh_field_query` (brute force over
+the faces: exact point-triangle distance, generalized winding number, attributes at the closest point),
+`primx_mesh_face_areas`, `primx_mesh_surface_points`, `primx_fps`.  Torch does the plumbing: the float64 inclusive sum of the
+areas (on the host, where it is sequential and therefore reproducible to the bit), the seeded uniforms (a CPU generator, as the
+sampler draws its noise), the normalisation and the assembly of `recon_param`.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import _lib, ops
+
+QUERY_CHUNK = 256          # triangle records per LDS chunk of primx_mesh_field_query (MF_CHUNK of csrc/meshfield.hip)
+RECORD_BYTES = 64
+N_ATTR = 5                 # r, g, b, roughness, metallic
+
+
+def _need_cuda(name, *tensors):
+    for t in tensors:
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise RuntimeError(f"{name} needs HIP device tensors; there is no CPU path")
+
+
+def _mesh_args(v, f):
+    v, f = v.float().contiguous(), f.int().contiguous()
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"v must be [V, 3] and f [F, 3], got {tuple(v.shape)} and {tuple(f.shape)}")
+    if v.shape[0] == 0 or f.shape[0] == 0:
+        raise ValueError("the mesh has no vertices or no faces")
+    return v, f
+
+
+@ops.on_input_device
+def mesh_field_query(x: torch.Tensor, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None):
+    """x [n, 3], v [V, 3] float32, f [F, 3] int32, attr [V, C] or None -> (dist [n], face [n] int32, wn [n], out_attr [n, C]
+    or None): primx_mesh_field_query.  Face indices outside [0, V) raise."""
+    _need_cuda("mesh_field_query", x, v, f, attr)
+    v, f = _mesh_args(v, f)
+    x = x.float().contiguous()
+    n, F, dev = x.shape[0], f.shape[0], x.device
+    C = 0 if attr is None else attr.shape[1]
+    if attr is not None:
+        attr = attr.float().contiguous()
+        if attr.shape[0] != v.shape[0]:
+            raise ValueError("attr must have one row per vertex")
+    dist = torch.empty(n, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    wn = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(n, C, dtype=torch.float32, device=dev) if C else None
+    ws = torch.empty(64 + RECORD_BYTES * F, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().primx_mesh_field_query(
+        ops._dev(x, "x", torch.float32), n, ops._dev(v, "v", torch.float32), ops._dev(f, "f", torch.int32), v.shape[0], F,
+        ops._dev(attr, "attr", torch.float32) if C else None, C, ws.data_ptr(), ws.numel(), dist.data_ptr(), face.data_ptr(),
+        wn.data_ptr(), out.data_ptr() if C else None, ops._stream()), "primx_mesh_field_query")
+    return dist, face, wn, out
+
+
+class MeshField:
+    """The signed distance, colour and material functions of a triangle mesh: `query(x)` -> {'sdf' [n, 1], 'tex' [n, 3],
+    'mat' [n, 2], 'face' [n], 'wn' [n]}.  sdf = the distance to the closest triangle outside and its negative inside, where
+    inside means |winding number| >= 0.5 (negative inside, as PrimSDF stores it); tex / mat are the vertex attributes at the
+    closest point, clipped to [0, 1] (zeros without attributes)."""
+
+    def __init__(self, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None):
+        _need_cuda("mesh_field", v, f, attr)
+        self.v, self.f = _mesh_args(v, f)
+        if attr is not None and tuple(attr.shape) != (self.v.shape[0], N_ATTR):
+            raise ValueError(f"attr must be [V, {N_ATTR}] (r, g, b, roughness, metallic), got {tuple(attr.shape)}")
+        self.attr = None if attr is None else attr.float().contiguous()
+
+    def query(self, x: torch.Tensor) -> dict:
+        dist, face, wn, a = mesh_field_query(x, self.v, self.f, self.attr)
+        sdf = torch.where(wn.abs() >= 0.5, -dist, dist)[:, None]
+        if a is None:
+            a = torch.zeros(x.shape[0], N_ATTR, dtype=torch.float32, device=dist.device)
+        a = a.clip(0, 1)
+        return {"sdf": sdf, "tex": a[:, 0:3], "mat": a[:, 3:5], "face": face, "wn": wn}
+
+    __call__ = query
+
+
+def mesh_field(v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None) -> MeshField:
+    return MeshField(v, f, attr)
+
+
+@ops.on_input_device
+def face_areas(v: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
+    """float64 [F]: primx_mesh_face_areas."""
+    _need_cuda("face_areas", v, f)
+    v, f = _mesh_args(v, f)
+    area = torch.empty(f.shape[0], dtype=torch.float64, device=v.device)
+    status = torch.empty(1, dtype=torch.int32, device=v.device)
+    _lib.check(_lib.load().primx_mesh_face_areas(ops._dev(v, "v", torch.float32), ops._dev(f, "f", torch.int32), v.shape[0],
+                                                 f.shape[0], area.data_ptr(), status.data_ptr(), ops._stream()),
+               "primx_mesh_face_areas")
+    return area
+
+
+def area_cdf(area: torch.Tensor) -> torch.Tensor:
+    """The inclusive float64 sum, taken on the host: sequential, so the same bits on every machine (a device scan adds in an
+    order of its own)."""
+    return torch.cumsum(area.double().cpu(), 0).to(area.device)
+
+
+def surface_uniforms(n: int, seed: int = 0) -> torch.Tensor:
+    """[n, 3] float32 in [0, 1) from a seeded CPU generator (the same numbers on every device)."""
+    return torch.rand(n, 3, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
+
+
+@ops.on_input_device
+def surface_points(v: torch.Tensor, f: torch.Tensor, cdf: torch.Tensor, u: torch.Tensor):
+    """cdf [F] float64 (inclusive), u [N, 3] in [0, 1) -> (pts [N, 3] float32, face [N] int32): primx_mesh_surface_points."""
+    _need_cuda("surface_points", v, f, cdf, u)
+    v, f = _mesh_args(v, f)
+    cdf, u = cdf.double().contiguous(), u.float().contiguous()
+    if cdf.shape != (f.shape[0],) or u.dim() != 2 or u.shape[1] != 3:
+        raise ValueError("cdf must be [F] and u [N, 3]")
+    N = u.shape[0]
+    pts = torch.empty(N, 3, dtype=torch.float32, device=v.device)
+    face = torch.empty(N, dtype=torch.int32, device=v.device)
+    status = torch.empty(1, dtype=torch.int32, device=v.device)
+    _lib.check(_lib.load().primx_mesh_surface_points(
+        ops._dev(v, "v", torch.float32), ops._dev(f, "f", torch.int32), v.shape[0], f.shape[0], ops._dev(cdf, "cdf", torch.float64),
+        ops._dev(u, "u", torch.float32), N, pts.data_ptr(), face.data_ptr(), status.data_ptr(), ops._stream()),
+        "primx_mesh_surface_points")
+    return pts, face
+
+
+@ops.on_input_device
+def fps(pts: torch.Tensor, K: int, start: int = 0):
+    """pts [N, 3] -> (idx [K] int32, nn [K] float32): primx_fps (ties to the lowest index; nn = the distance from each chosen
+    centre to the nearest other one, 0 when K == 1)."""
+    _need_cuda("fps", pts)
+    pts = pts.float().contiguous()
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"pts must be [N, 3], got {tuple(pts.shape)}")
+    N, dev = pts.shape[0], pts.device
+    idx = torch.empty(K, dtype=torch.int32, device=dev)
+    nn = torch.empty(K, dtype=torch.float32, device=dev)
+    ws = torch.empty(((4 * N + 7) & ~7) + 4096, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().primx_fps(ops._dev(pts, "pts", torch.float32), N, K, start, ws.data_ptr(), ws.numel(),
+                                     idx.data_ptr(), nn.data_ptr(), ops._stream()), "primx_fps")
+    return idx, nn
+
+
+def normalize_vertices(v: torch.Tensor, extent: float = 0.9):
+    """fp32: the bounding box's centre to the origin, its longest half side to `extent` -> (v', centre [3], scale).  The
+    value 0.9 is this project's choice (PrimSDF's domain is [-1, 1]^3 and the outermost primitives reach past their
+    centres); the reference's own normalisation of its training meshes is not in its tree."""
+    lo, hi = v.min(0).values, v.max(0).values
+    c = (lo + hi) * 0.5
+    half = float(((hi - lo) * 0.5).max())
+    if not half > 0:
+        raise ValueError("the mesh has no extent")
+    s = torch.tensor(extent / half, dtype=torch.float32, device=v.device)     # rounded to fp32 once, on the host
+    return (v - c) * s, c, s
+
+
+def _local_grid(S: int, dev) -> torch.Tensor:
+    xx = torch.linspace(-1, 1, S)                                             # PrimSDF's own table (models/primsdf.py:35-41)
+    mx, my, mz = torch.meshgrid(xx, xx, xx, indexing="ij")
+    return torch.stack((mz, my, mx), dim=-1).reshape(-1, 3).to(dev)
+
+
+def _mesh_parts(mesh, dev):
+    if isinstance(mesh, (tuple, list)):
+        v, f, albedo, rough, metal = mesh
+    else:
+        v, f, albedo, rough, metal = mesh.v, mesh.f, mesh.albedo, mesh.roughness, mesh.metallic
+    t = lambda a: torch.as_tensor(a).to(dev)   # noqa: E731
+    v, f = t(v).float(), t(f).int()
+    attr = torch.cat([t(albedo).float().reshape(-1, 3), t(rough).float().reshape(-1, 1), t(metal).float().reshape(-1, 1)], 1)
+    return v, f, attr.contiguous()
+
+
+def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candidates: Optional[int] = None, seed: int = 0,
+                       normalize: bool = True, extent: float = 0.9, device=None, chunk: int = 1 << 20):
+    """mesh: a `mesh.TriMesh` or (v, f, albedo [V, 3], roughness [V], metallic [V]) -> (recon_param [P, 4 + 6 S^3], info).
+
+    `candidates` (default 32 P) surface samples drawn with `seed`; P of them by farthest point sampling from candidate 0;
+    scale = distance to the nearest other centre; payload in `PrimSDF.feat_param`'s layout [sdf | rgb | roughness, metallic],
+    each [z][y][x], evaluated at pos + scale * local_grid; colours and materials clipped to [0, 1], the SDF raw
+    (`primitives_to_latents` applies the x5).  `normalize`: see `normalize_vertices`.  `info` has the normalisation
+    (`center`, `scale`: v' = (v - center) * scale), the candidates (`candidates`, `candidate_face`) and the chosen ones (`idx`)."""
+    if device is None:
+        v0 = mesh[0] if isinstance(mesh, (tuple, list)) else mesh.v
+        device = v0.device if isinstance(v0, torch.Tensor) and v0.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    P, S = int(num_prims), int(prim_shape)
+    N = int(candidates) if candidates is not None else 32 * P
+    if not 1 <= P <= N:
+        raise ValueError(f"num_prims must lie in 1 .. candidates (got {P} of {N})")
+    with torch.cuda.device(dev), torch.no_grad():
+        v, f, attr = _mesh_parts(mesh, dev)
+        v, f = _mesh_args(v, f)
+        center, scale = torch.tensor([0.0, 0.0, 0.0], device=dev), torch.tensor(1.0, device=dev)
+        if normalize:
+            v, center, scale = normalize_vertices(v, extent)
+        cdf = area_cdf(face_areas(v, f))
+        cand, cface = surface_points(v, f, cdf, surface_uniforms(N, seed).to(dev))
+        idx, nn = fps(cand, P, 0)
+        pos = cand[idx.long()]
+        x = (pos[:, None, :] + nn[:, None, None] * _local_grid(S, dev)[None]).reshape(-1, 3)
+        field = MeshField(v, f, attr)
+        parts = [field.query(x[lo:lo + chunk]) for lo in range(0, x.shape[0], chunk)]
+        sdf = torch.cat([q["sdf"] for q in parts]).reshape(P, S ** 3)
+        a = torch.cat([torch.cat([q["tex"], q["mat"]], 1) for q in parts]).reshape(P, S ** 3, N_ATTR)
+        recon = torch.cat([nn[:, None], pos, sdf, a.transpose(1, 2).reshape(P, -1)], 1).contiguous()
+    info = {"center": center, "scale": scale, "v": v, "f": f, "attr": attr, "candidates": cand, "candidate_face": cface, "idx": idx}
+    return recon, info
+
+
+def primsdf_from_mesh(cls, mesh, num_prims: int = 2048, prim_shape: int = 8, return_info: bool = False, **kw):
+    """`PrimSDF.from_mesh`: a module in eval mode on the mesh's device holding `mesh_to_primitives(mesh, ...)`, ready for
+    `query`, `mesh.extract_mesh` and `pipeline.primitives_to_latents` (through `recon_param`)."""
+    recon, info = mesh_to_primitives(mesh, num_prims=num_prims, prim_shape=prim_shape, **kw)
+    m = cls(num_prims=recon.shape[0], dim_feat=6, prim_shape=prim_shape)
+    m.srt_param = torch.nn.Parameter(recon[:, :4].contiguous(), requires_grad=False)
+    m.feat_param = torch.nn.Parameter(recon[:, 4:].contiguous(), requires_grad=False)
+    m = m.to(recon.device).eval()
+    return (m, info) if return_info else m

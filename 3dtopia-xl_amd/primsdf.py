@@ -4,8 +4,9 @@ extraction of inference.py:106-116, 180-193).
 `PrimSDF` mirrors the reference module's parameters (`srt_param` [P, 1 + 3] = scale + translation, `feat_param`
 [P, 6 * S^3]), its properties (`pos`, `scale`, `feat`, `feat_geo`, `feat_tex`, `feat_mat`) and `forward(x) ->
 {'sdf', 'tex', 'mat'}` including the inference-time fill of uncovered points; the evaluation itself is one HIP kernel
-(`primx_primsdf_query`).  The fitting path (`_init_param`, which needs trimesh and a mesh SDF) is training-side and not
-part of this package.
+(`primx_primsdf_query`).  The reference's fitting path (`_init_param`, an empty `pass` in its tree) is not mirrored: the
+constructor still refuses `f_sdf` / `geo_fn` / `asset_list`.  `PrimSDF.from_mesh` fits primitives to a triangle mesh instead
+(fit.py: the initialisation the paper describes, without its gradient refinement).
 """
 from __future__ import annotations
 
@@ -41,6 +42,14 @@ class PrimSDF(nn.Module):
     feat_geo = property(lambda self: self.feat_param[:, self.geo_start_index:self.geo_end_index])
     feat_tex = property(lambda self: self.feat_param[:, self.tex_start_index:self.tex_end_index])
     feat_mat = property(lambda self: self.feat_param[:, self.mat_start_index:self.mat_end_index])
+
+    @classmethod
+    def from_mesh(cls, mesh, num_prims=2048, prim_shape=8, **kw):
+        """A module holding `fit.mesh_to_primitives(mesh, num_prims, prim_shape, **kw)`, in eval mode on the HIP device: ready
+        for `query`, `mesh.extract_mesh` and (as `torch.cat([srt_param, feat_param], 1)[None]`) `primitives_to_latents`.
+        `return_info=True` also returns the fit's `info`."""
+        from . import fit
+        return fit.primsdf_from_mesh(cls, mesh, num_prims=num_prims, prim_shape=prim_shape, **kw)
 
     def sdf2alpha(self, sdf):
         return torch.exp(-(sdf / self.sdf2alpha_var) ** 2)

@@ -81,7 +81,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 32
+#define PRIMX_ABI_VERSION 33
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -874,6 +874,49 @@ int primx_layernorm_modulate_f32(const float* x, const float* shift, const float
 
 /* out = x * sigmoid(x), fp32: the nn.SiLU in front of every adaLN Linear (models/dit_crossattn.py:40-43,69-72). */
 int primx_silu_f32(const float* in, float* out, int64_t n, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Primitive fitting (ABI 33, csrc/meshfield.hip): the initialisation the 3DTopia-XL paper describes - surface samples,
+ * farthest point sampling, scale = distance to the nearest other centre, payload = the mesh's signed distance, colour
+ * and material at every voxel.  The reference's PrimSDF._init_param is an empty `pass` (models/primsdf.py:48-50): there
+ * is no reference code; tests/meshfield_numpy.py restates the rules below in float64 / float32.  Every expression is
+ * evaluated as written, uncontracted; dot(a, b) = (ax bx + ay by) + az bz.  All four calls synchronise the stream once
+ * where they read back the index check (status / the head of ws); face indices outside [0, V) return PRIMX_EINVAL.
+ * -------------------------------------------------------------------------------------------- */
+
+/* Brute-force field query: pts [n, 3], v [V, 3], f [F, 3], attr [V, C] (C in 0 .. 16; C = 0: attr / out_attr unused) ->
+ * dist [n] (distance to the closest triangle), face [n] (its index: the first minimum of the squared distance in face
+ * order), wn [n] (generalized winding number), out_attr [n, C].  Per point p and face (a, b, c), with ab = b - a,
+ * ac = c - a, ap = p - a, bp = p - b, cp = p - c:
+ *   - closest point q = (a + ab v) + ac w by Ericson's seven Voronoi regions, tested in the order A, B, AB, C, AC, BC, face with
+ *     d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp, vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6,
+ *     va = d3 d6 - d5 d4: AB (v, w) = (d1, 0) / (d1 - d3); AC (0, d2) / (d2 - d6); BC w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),
+ *     v = 1 - w; face (vb, vc) / ((va + vb) + vc); x / den is x * (1 / den), and 0 where den == 0.  Squared distance |p - q|^2;
+ *     in a vertex region |ap|^2, |bp|^2 or |cp|^2 and (v, w) = (0, 0), (1, 0), (0, 1).
+ *   - a face whose ab x ac is the zero vector is measured as its longest edge (ab, ac, bc: the first of equals; a point is an
+ *     edge of length 0): t = clamp(dot(p - start, e) / dot(e, e), 0, 1), t = 0 when dot(e, e) == 0; it adds 0 to wn.
+ *   - wn = (sum over faces, in face order, of atan2(-ap.(bp x cp), |ap||bp||cp| + (ap.bp)|cp| + (bp.cp)|ap| + (cp.ap)|bp|))
+ *     * (1 / 2 pi): the Van Oosterom-Strackee solid angle 2 atan2(...) over 4 pi; +1 inside an outward-oriented closed mesh.
+ *   - out_attr = (attr[f0] (1 - v - w) + attr[f1] v) + attr[f2] w at the (v, w) of `face`.
+ * No output is NaN for finite input.  ws: 64 + 64 F bytes, 16-byte aligned, any contents (face records + the index flag).
+ * The point index is 64 bits wide; 3 V and 4 F must stay below 2^31. */
+int primx_mesh_field_query(const float* pts, int64_t n, const float* v, const int* f, int V, int F, const float* attr, int C,
+                           void* ws, int64_t ws_bytes, float* dist, int* face, float* wn, float* out_attr, void* stream);
+
+/* area [F] float64 = 0.5 |(b - a) x (c - a)| in float64 from the float32 vertices.  status: one int of scratch. */
+int primx_mesh_face_areas(const float* v, const int* f, int V, int F, double* area, int* status, void* stream);
+
+/* Area-weighted surface samples: cdf [F] = the inclusive float64 sum of the areas, u [N, 3] in [0, 1).  Sample i lies on the
+ * first face whose cdf exceeds (double)u0 * cdf[F - 1] (binary search; the last face if none does) at
+ * ((1 - r) A + r (1 - u2) B) + (r u2) C, r = sqrt(u1), in fp32.  -> pts [N, 3], face [N].  status: one int of scratch. */
+int primx_mesh_surface_points(const float* v, const int* f, int V, int F, const double* cdf, const float* u, int64_t N,
+                              float* pts, int* face, int* status, void* stream);
+
+/* Farthest point sampling of K of the N points pts [N, 3] in fp32: idx[0] = start; every candidate keeps the minimum of
+ * d2 = (dx dx + dy dy) + dz dz to the centres chosen so far; the next centre is the candidate with the largest minimum, the
+ * lowest index among equals.  nn [K] = sqrt of the smallest d2 from centre k to another entry of idx (0 when K == 1).
+ * One launch per centre, no host synchronisation; ws: 4 N (rounded up to 8) + 4096 bytes, 8-byte aligned, any contents. */
+int primx_fps(const float* pts, int N, int K, int start, void* ws, int64_t ws_bytes, int* idx, float* nn, void* stream);
 
 #ifdef __cplusplus
 }
