@@ -1676,14 +1676,17 @@ __global__ void xcd_probe_kernel() {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     if (threadIdx.x == 0) g_xcd_probe[blockIdx.x] = xcc & 15;
 }
-static bool xcd_mapping_ok() {
+static bool xcd_mapping_ok(hipStream_t st) {
     static int state[64] = {0};   // per device: 0 unknown, 1 ok, -1 not
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
     if (state[dev] == 0) {
+        // the probe and its read-back go to the CALLER's stream (the one host synchronisation of this entry point, once per
+        // device and process): stream 0 is not ours to launch on or to wait for
         unsigned h[256];
-        hipLaunchKernelGGL(xcd_probe_kernel, dim3(256), dim3(64), 0, 0);
-        bool ok = hipMemcpyFromSymbol(h, HIP_SYMBOL(g_xcd_probe), sizeof(h)) == hipSuccess;
+        hipLaunchKernelGGL(xcd_probe_kernel, dim3(256), dim3(64), 0, st);
+        bool ok = hipMemcpyFromSymbolAsync(h, HIP_SYMBOL(g_xcd_probe), sizeof(h), 0, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipStreamSynchronize(st) == hipSuccess;
         for (int i = 0; ok && i < 256; ++i) ok = h[i] == h[i & 7];
         for (int i = 0; ok && i < 8; ++i)
             for (int j = 0; j < i; ++j) ok = ok && h[i] != h[j];
@@ -1828,7 +1831,7 @@ void launch144_dma(const GemmArgs<DT>& a, int mt, hipStream_t st) {
                 const int nt = x.N / 144;
                 if (x.ln_out && x.sync && g_ln_fuse && x.N == 1152 && mt % 8 == 0 && (int)grid.x <= g_ln_maxgrid && nt * 8 <= 128 &&
                     (((uintptr_t)x.ln_shift | (uintptr_t)x.ln_scale | (uintptr_t)x.ln_out) & 7) == 0 && x.ln_mod_stride % 4 == 0 &&
-                    xcd_mapping_ok()) {
+                    xcd_mapping_ok(st)) {
                     PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI_GATE_RESIDUAL_LN);
                     hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI_GATE_RESIDUAL_LN>), grid, dim3(640), 0, st, PRIMX_GEMM_PASS(x));
                     g_ln_fused = true;

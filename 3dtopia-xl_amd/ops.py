@@ -380,7 +380,9 @@ def linear_f32out_group(problems: Sequence[Tuple[torch.Tensor, torch.Tensor, Opt
                      N | (first << 32)])                          # (N, first_wg: two little-endian ints in the struct's last 8 bytes)
         first += (N + 127) // 128
         flops += 2.0 * M * N * K
-    table = torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=False)
+    # (from pinned memory, not blocking: the host does not wait for the stream; torch's host allocator keeps the pinned block
+    # from being reused until the copy, which is ordered on the launch stream, has run)
+    table = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
     _timed(f"None {len(problems)} problems x {M} rows, K = {K}", flops, lambda: check(_lib.load().primx_linear_f32out_group(
         table.data_ptr(), len(problems), first, M, K, bias_from_row, dtype_code(dt), _stream()), "primx_linear_f32out_group"))
     return True
@@ -534,7 +536,7 @@ def alloc_heads(B: int, H: int, n: int, dh: int, kind: int, dtype: torch.dtype, 
         k = torch.arange(n, device=device)
         quad = (k >> 2) & 3
         pos = (k & ~15) | ((((quad & 1) << 1) | (quad >> 1)) << 2) | (k & 3)
-        buf[:, :, dh, pos] = 1.0
+        buf[:, :, dh].index_fill_(2, pos, 1.0)    # (not `buf[:, :, dh, pos] = 1.0`: torch uploads that scalar with a blocking copy)
     return buf
 
 

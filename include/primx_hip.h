@@ -11,6 +11,8 @@
  *     state between calls that changes what a later call does (ABI 21: the cache-prefetch ranges
  *     that GEMM / LayerNorm launches can carry are explicit arguments of the carrying call).
  *     Work is enqueued on `stream` and is asynchronous with respect to the host.
+ *     (Held by tests/test_hip_streams.py with tests/streamorder.py: every entry point that takes a `stream` runs on a side stream
+ *     behind late-produced operands while stream 0 is blocked; the hosts that synchronise by design are listed there.)
  *   - `dtype` selects the 16-bit storage/MFMA-input type of activations and weights:
  *     PRIMX_F16 or PRIMX_BF16.  Accumulation is always fp32.
  *

@@ -279,6 +279,11 @@ class Guard:
         off = (self._n * 7919) % (pool.numel() - n + 1)
         return pool[off:off + n]
 
+    def prime(self, device) -> None:
+        """Upload the guard pattern of `device` now (a blocking copy) instead of at the first allocation: tests/streamorder.py
+        allocates behind a blocked stream, where the host must not wait."""
+        self._pattern(_device_of(device), 1)
+
     def _alloc(self, shape, strides, dtype, device, value, site: str, what: str, span: Optional[int] = None) -> torch.Tensor:
         """`span`: elements of the payload when the view is strided (guard_input); default the product of `shape`."""
         item = _itemsize(dtype)
