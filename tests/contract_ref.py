@@ -601,26 +601,187 @@ def attn_bound(q, k, v, scale, dtype, same_p):
     return outs, bounds
 
 
-def attn_check(got, q, k, v, scale, dtype, same_p, what):
-    out, E = attn_bound(q, k, v, scale, dtype, same_p)
-    out_np = out.cpu().numpy()
-    bound = 0.5 * ulp16(out_np, dtype) + E.cpu().numpy()
+def attn_report(got, q, k, v, scale, dtype, same_p, ref=None):
+    """(ratio, signed) without an assertion: ratio = max |err| / bound (NaN when `got` holds a NaN), signed = the signed errors
+    in ulps of the result, sign taken along the result, over the elements that do not cancel to near zero (the sample of the
+    bias criterion below).  ref = attn_bound's (out, E) as numpy arrays when the caller holds several outputs to one input."""
+    if ref is None:
+        out, E = attn_bound(q, k, v, scale, dtype, same_p)
+        ref = out.cpu().numpy(), E.cpu().numpy()
+    out_np, E_np = ref
+    bound = 0.5 * ulp16(out_np, dtype) + E_np
     g = _f64(got).reshape(out_np.shape)
-    err = np.abs(g - out_np)
-    ratio = float(np.max(err / bound))
-    print(f"attention {what} {dtype}: max |err| / bound = {ratio:.3f}")
+    ratio = float(np.max(np.abs(g - out_np) / bound))
+    rms = float(np.sqrt(np.mean(out_np ** 2)))
+    sel = np.abs(out_np) >= 0.25 * rms
+    signed = (g - out_np)[sel] * np.sign(out_np[sel]) / ulp16(out_np[sel], dtype)
+    return ratio, signed
+
+
+def attn_check(got, q, k, v, scale, dtype, same_p, what, bias=True, quiet=False):
+    """bias=False: only the bound is asserted and (ratio, signed errors) come back, for a caller that pools the bias statistic
+    over many cells (tests/test_hip_attention_grid.py): on one tiny cell it is taken over too few values, and under the sentinel
+    patterns of attn_inputs the correctly rounded result itself is biased (the residual weight pulls every element one way)."""
+    ratio, signed = attn_report(got, q, k, v, scale, dtype, same_p)
+    if not quiet:
+        print(f"attention {what} {dtype}: max |err| / bound = {ratio:.3f}")
     assert ratio <= ATTN_SLACK, f"attention {what} {dtype}: error {ratio:.3f} x the derived bound"
+    if not bias:
+        return ratio, signed
     # no bias: the mean signed error in ulps of the result, over the elements that do not cancel to near zero.  Asserted where
     # every documented approximation is unbiased (P rounded to nearest).  The dh = 72 path packs P toward zero by design: a key
     # at the running max keeps p = 1 exactly while every other key loses 2^-11 (fp16) / 2^-8 (bf16) of its weight on average,
     # which pulls the output towards the dominant key's value - inside the bound above, but a bias; it is reported only.
-    rms = float(np.sqrt(np.mean(out_np ** 2)))
-    sel = np.abs(out_np) >= 0.25 * rms
-    bias = float(np.mean((g - out_np)[sel] * np.sign(out_np[sel]) / ulp16(out_np[sel], dtype)))
-    print(f"attention {what} {dtype}: mean signed error {bias:+.3f} ulp")
+    mean_signed = float(np.mean(signed))
+    print(f"attention {what} {dtype}: mean signed error {mean_signed:+.3f} ulp")
     if not same_p:
-        assert abs(bias) <= BIAS_LIMIT, f"attention {what} {dtype}: biased by {bias:.3f} ulp"
+        assert abs(mean_signed) <= BIAS_LIMIT, f"attention {what} {dtype}: biased by {mean_signed:.3f} ulp"
     return ratio
+
+
+# Inputs under which EACH KEY decides the result.  Dense random inputs give one key of nkv a weight of about 1 / nkv, which is
+# inside the approximation error the bound above grants: an off-by-one in the key mask ships unnoticed (pinned by
+# tests/test_attention_grid_cpu.py::test_random_inputs_alone_miss_the_unmasked_pad).  Two sentinel patterns close that:
+#   lookup: k rows N(0, 1) scaled to |k_j| = sqrt(dh), q_i = 3 k_j(i) with j(i) = (nkv - 1 - i) mod nkv (query 0 looks up the LAST
+#           valid key), v N(0, 1).  The chosen key's logit is 3 sqrt(dh), the others' are N(0, 9): out_i ~ v_j(i), and a dropped,
+#           swapped or misplaced key, a skipped tile or a V^T tile paired with the wrong K tile moves the affected rows by O(1);
+#   trap:   q, k = 0.3 N(0, 1) with q[..., 0] = c, k[..., 0] = -c, c = sqrt(17 sqrt(dh)): every real logit is about -17 nats, so a
+#           pad key that reaches the softmax with score 0 takes all the weight and the row (v = 1 + 0.5 N(0, 1)) collapses from
+#           about 1 to about 0.  On the dh = 72 path the first tile's max is a large NEGATIVE step from the initial m_run = 0.
+# The numbers come from a CPU generator whatever the device, so the CPU proof and the GPU grid see the same tensors.
+ATTN_PATTERNS = ("random", "lookup", "trap")
+ATTN_SIGMAS = (0.5, 4.0, 16.0)
+
+
+def attn_inputs(pattern, seed, B, Mq, Mk, H, dh, device, sigma=1.0):
+    """fp32 q [B, Mq, H, dh], k, v [B, Mk, H, dh] on `device` (the caller rounds them to the 16-bit type); sigma: `random` only."""
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda n: torch.randn(B, n, H, dh, generator=g)
+    if pattern == "random":
+        q, k, v = rn(Mq) * sigma, rn(Mk), rn(Mk)
+    elif pattern == "lookup":
+        k = rn(Mk)
+        k = k * (dh ** 0.5 / k.norm(dim=-1, keepdim=True))
+        q = 3.0 * k[:, (Mk - 1 - torch.arange(Mq)) % Mk]
+        v = rn(Mk)
+    elif pattern == "trap":
+        c = (17.0 * dh ** 0.5) ** 0.5
+        q, k, v = 0.3 * rn(Mq), 0.3 * rn(Mk), 1.0 + 0.5 * rn(Mk)
+        q[..., 0], k[..., 0] = c, -c
+    else:
+        raise ValueError(pattern)
+    return q.to(device), k.to(device), v.to(device)
+
+
+def trunc16(x, dtype) -> np.ndarray:
+    """fp32 x >= 0 -> the 16-bit value TOWARD ZERO as fp32: v_cvt_pkrtz_f16_f32 (subnormals kept) / the upper half of the fp32 word."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if dtype == torch.bfloat16:
+        return (x.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+    h = x.astype(np.float16)
+    h = np.where(h.astype(np.float32) > x, np.nextafter(h, np.float16(0)), h)
+    return h.astype(np.float32)
+
+
+# One injected bug each, for the teeth tests of tests/test_attention_grid_cpu.py; attn_fault_applies tells where it changes
+# the arithmetic at all (elsewhere the faulted restatement is bit-identical to the unfaulted one, which the test asserts too).
+ATTN_FAULTS = {
+    "pad_last_key": "the last valid key is treated as a pad",
+    "unmask_first_pad": "the first pad key is unmasked (operands laid out for nkv + 1 keys: zero K row, zero V column)",
+    "skip_last_tile": "the last key tile is skipped",
+    "stale_stage": "the last tile j is read from the ring stage of tile j - 3",
+    "v_of_previous_tile": "V(j) is paired with K(j + 1)",
+    "no_rescale": "O is not rescaled when the running max rises",
+    "no_quad_order": "the V^T quad order {0, 2, 1, 3} is not applied",
+    "row_from_32_above": "query rows 32 .. 63 are computed from the rows 32 above them",
+    "denominator_before_mask": "overwrite path: the denominator is summed before the scores past nkv are overwritten",
+}
+
+
+def attn_fault_applies(fault, nq, nkv, same_p) -> bool:
+    nt = (nkv + 63) // 64
+    return {"pad_last_key": True, "unmask_first_pad": nkv % 64 != 0, "skip_last_tile": True, "stale_stage": nt >= 4,
+            "v_of_previous_tile": nt >= 2, "no_rescale": nt >= 2, "no_quad_order": nkv > 4,
+            "row_from_32_above": nq > 32 and nkv > 1, "denominator_before_mask": not same_p and nkv % 64 != 0}[fault]
+
+
+def attn16_restate(q, k, v, scale, dtype, same_p, fault=None):
+    """numpy restatement of the algorithm attn_kernel / attn64_kernel document (the comment block above attn_bound, the header of
+    csrc/attention.hip): q [G, Mq, dh], k, v [G, nkv, dh] holding 16-bit values (G = batch x heads) -> [G, Mq, dh] float64 of 16-bit
+    values.  64-key tiles; a running max that is raised - O rescaled - only when some row of a 32-row wave has a tile max more
+    than 2^8 above it; fp32 O and row sum, one reciprocal, one final rounding.
+      same_p (dh = 72): Q pre-scaled by c = scale log2(e) and rounded to 16 bits; the max is subtracted as two 16-bit halves inside
+        the score sum; P = exp2(score) packed toward zero and used for BOTH sums (the all-ones row of V^T, valid keys only); the
+        pad keys carry -30000 in the mask column of K.  m_run starts at 0 and the first tile always rescales.
+      else (dh = 64 / 32, and attn64_kernel = the one-tile case): raw fp32 scores, those past nkv overwritten with -1e30;
+        P = exp2(s c - m c), rounded to nearest for the numerator, summed unrounded for the denominator.
+    Not bit-faithful (numpy's matmul stands for the MFMA chains, float64 for the short sum of score terms).  fault: a key of ATTN_FAULTS."""
+    f4 = np.float32
+    q, k, v = (np.ascontiguousarray(t, dtype=f4) for t in (q, k, v))
+    G, Mq, dh = q.shape
+    nkv = k.shape[1]
+    c = f4(f4(scale) * f4(1.4426950408889634))
+    nt = (nkv + 63) // 64
+    if fault == "row_from_32_above":
+        q = q.copy()
+        q[:, 32:64] = q[:, :max(min(Mq, 64) - 32, 0)]
+    valid = nkv - 1 if fault == "pad_last_key" else nkv + 1 if fault == "unmask_first_pad" and nkv % 64 else nkv
+    Kp, Vp = np.zeros((G, 64 * nt, dh), f4), np.zeros((G, 64 * nt, dh), f4)
+    Kp[:, :nkv], Vp[:, :nkv] = k, v
+    key = np.arange(64 * nt)
+    ones = (key < valid).astype(f4)                                            # row dh of V^T
+    maskcol = np.where(key < valid, 0.0, round16(-30000.0, dtype)).astype(f4)  # column dh of K (against Q's 1)
+    if fault == "no_quad_order":
+        quad = (key >> 2) & 3
+        Vp = Vp[:, (key & ~15) | ((((quad & 1) << 1) | (quad >> 1)) << 2) | (key & 3)]
+
+    def wave_any(t):                                                           # __all / __any over the 32 rows of a wave
+        a = np.pad(t, ((0, 0), (0, (-Mq) % 32))).reshape(G, -1, 32).any(-1)
+        return np.repeat(a, 32, axis=1)[:, :Mq]
+
+    O, l = np.zeros((G, Mq, dh), f4), np.zeros((G, Mq), f4)
+    if same_p:
+        qs = round16(q * c, dtype).astype(f4)
+        m_run, mh, ml = np.zeros((G, Mq), f4), np.zeros((G, Mq)), np.zeros((G, Mq))   # mh, ml: -m_hi, -m_lo as Q carries them
+    else:
+        m_run = np.full((G, Mq), -1e30, f4)
+    with np.errstate(under="ignore", over="ignore", invalid="ignore", divide="ignore"):
+        for t in range(nt - 1 if fault == "skip_last_tile" else nt):
+            kt = t - 3 if fault == "stale_stage" and t == nt - 1 and t >= 3 else t
+            vt = max(t - 1, 0) if fault == "v_of_previous_tile" else kt
+            Kt, Vt = Kp[:, 64 * kt:64 * kt + 64], Vp[:, 64 * vt:64 * vt + 64]
+            if same_p:
+                s = (np.matmul(qs.astype(np.float64), Kt.transpose(0, 2, 1).astype(np.float64)) + maskcol[64 * kt:64 * kt + 64]
+                     + mh[..., None] + ml[..., None]).astype(f4)
+                mx = s.max(-1)
+                trig = np.ones_like(mx, bool) if t == 0 else wave_any(mx > 8.0)
+                delta = np.where(trig, mx if t == 0 else np.maximum(mx, 0), 0).astype(f4)
+                alpha = np.exp2(-delta)
+                if fault != "no_rescale":
+                    O, l = O * alpha[..., None], l * alpha
+                m_run = m_run + delta
+                mh = round16(-m_run, dtype)
+                ml = round16(-m_run.astype(np.float64) - mh, dtype)
+                P = trunc16(np.exp2(s - delta[..., None]), dtype)
+                l = l + np.matmul(P, ones[64 * vt:64 * vt + 64])
+                O = O + np.matmul(P, Vt)
+            else:
+                raw = np.matmul(q, Kt.transpose(0, 2, 1))
+                s = np.where(key[64 * t:64 * t + 64] >= valid, f4(-1e30), raw)
+                mx = s.max(-1)
+                trig = wave_any((mx - m_run) * c > 8.0)
+                m_new = np.where(trig, np.maximum(m_run, mx), m_run)
+                alpha = np.exp2((m_run - m_new) * c)
+                l = l * alpha
+                if fault != "no_rescale":
+                    O = O * alpha[..., None]
+                m_run = m_new
+                mc = (m_run * c)[..., None]
+                P = np.exp2(s * c - mc)
+                l = l + (np.exp2(raw * c - mc) if fault == "denominator_before_mask" else P).sum(-1, dtype=f4)
+                O = O + np.matmul(round16(P, dtype).astype(f4), Vt)
+        out = O * (f4(1.0) / l)[..., None]
+    return round16(out, dtype)
 
 
 # ------------------------------------------------------------------------------------------------ the fp32 entry points
