@@ -126,16 +126,20 @@ def redenoise_primitives(recon_param: torch.Tensor, vae, model, diffusion, y: to
                          generator=None, cfg_scale: float = 6.0, invert_cfg_scale: float = 1.0,
                          precision_dtype: torch.dtype = torch.float16, enable_amp: bool = True,
                          latent_mean: Optional[Sequence[float]] = None, latent_std: Optional[Sequence[float]] = None,
-                         latent_nf: float = 1.0) -> torch.Tensor:
+                         latent_nf: float = 1.0, sampler: str = "ddim") -> torch.Tensor:
     """recon_param (B, N_prim, 4 + 6 * 8^3) -> recon_param of the edited asset: `primitives_to_latents`, then the tokens are
     taken to level `start_step` of `diffusion` - mode "noise": `q_sample` with `noise` (drawn once with `generator` when None);
     mode "invert": `ddim_reverse_sample_loop(stop_step=start_step)` under `model.forward_with_cfg` at `invert_cfg_scale` - and
     `ddim_sample_loop(start_step=start_step)` re-denoises them under the conditioning `y` at `cfg_scale`; `latents_to_primitives`
     decodes.  `keep` (bool; (B, N_prim) keeps whole primitives, (B, N_prim, 68) elements, see `keep_mask`) holds those tokens
     on the input asset's own trajectory: they come out as the encode -> decode round trip of the input, bit for bit.  `keep`
-    needs mode "noise": the kept rows of an inversion would need the inversion's own implied noise."""
+    needs mode "noise": the kept rows of an inversion would need the inversion's own implied noise.  `sampler` "dpm" re-denoises
+    with `dpm_solver_sample_loop` (DPM-Solver++(2M), for processes of 10 to 15 steps) in place of `ddim_sample_loop`: the same
+    `start_step` and `keep`, nothing drawn differently, the same contract for the kept tokens."""
     if mode not in ("noise", "invert"):
         raise ValueError(f'mode must be "noise" or "invert", got {mode!r}')
+    if sampler not in ("ddim", "dpm"):
+        raise ValueError(f'sampler must be "ddim" or "dpm", got {sampler!r}')
     if keep is not None and mode == "invert":
         raise ValueError('keep needs mode="noise": an inverted trajectory has no noise tensor to hold the kept tokens on')
     if not (0 <= int(start_step) < diffusion.num_timesteps):
@@ -155,8 +159,9 @@ def redenoise_primitives(recon_param: torch.Tensor, vae, model, diffusion, y: to
             level = diffusion.ddim_reverse_sample_loop(model.forward_with_cfg, tokens, clip_denoised=False,
                                                        model_kwargs=dict(kw, cfg_scale=invert_cfg_scale), stop_step=start_step)
         held = {} if keep is None else dict(known=tokens, keep=keep, known_noise=noise)
-        samples = diffusion.ddim_sample_loop(model.forward_with_cfg, tuple(tokens.shape), noise=level, clip_denoised=False,
-                                             model_kwargs=kw, start_step=start_step, **held)
+        loop = diffusion.ddim_sample_loop if sampler == "ddim" else diffusion.dpm_solver_sample_loop
+        samples = loop(model.forward_with_cfg, tuple(tokens.shape), noise=level, clip_denoised=False, model_kwargs=kw,
+                       start_step=start_step, **held)
     return latents_to_primitives(samples, vae, latent_mean, latent_std, latent_nf)
 
 

@@ -8,7 +8,7 @@ others come out as the encode -> decode round trip of the input, bit for bit.  W
 carries random weights (as examples/generate.py): the outputs are noise, the point is the data flow and the per-stage timing.
 
     python examples/edit.py [--denoised IN.pt] [--out OUT.pt] [--steps 25] [--start-step 12] [--normal 1 0 0] [--offset 0]
-                            [--mode noise|invert] [--dit DIT.pt] [--vae VAE.pt] [--small]
+                            [--mode noise|invert] [--sampler ddim|dpm] [--dit DIT.pt] [--vae VAE.pt] [--small]
 """
 import argparse
 import os
@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--normal", type=float, nargs=3, default=[1.0, 0.0, 0.0])
     ap.add_argument("--offset", type=float, default=0.0)
     ap.add_argument("--mode", choices=["noise", "invert"], default="noise", help="invert: DDIM inversion, regenerates everything")
+    ap.add_argument("--sampler", choices=["ddim", "dpm"], default="ddim", help="dpm: generate and re-denoise with DPM-Solver++(2M) "
+                    "over the same ddim<steps> grid (e.g. --steps 12 --start-step 6)")
     ap.add_argument("--dit", default=None, help="DiT checkpoint (.pt with 'ema'); synthetic weights when absent")
     ap.add_argument("--vae", default=None, help="VAE checkpoint (.pt with 'model_state_dict'); synthetic weights when absent")
     ap.add_argument("--small", action="store_true", help="tiny networks (smoke run)")
@@ -74,7 +76,7 @@ def main():
         t0 = time.perf_counter()
         r = fn()
         torch.cuda.synchronize()
-        print(f"{name:44s} {1e3 * (time.perf_counter() - t0):9.2f} ms", flush=True)
+        print(f"{name:52s} {1e3 * (time.perf_counter() - t0):9.2f} ms", flush=True)
         return r
 
     image = torch.rand(1, 3, img, img, device=dev)
@@ -85,8 +87,9 @@ def main():
         recon = torch.cat([sd["srt_param"], sd["feat_param"]], dim=-1)[None].float().to(dev)
     else:
         x = torch.randn(1, n_prims, 68).to(dev)
-        samples = timed(f"DDIM loop, {a.steps} steps, CFG 6 (first call)",
-                        lambda: diffusion.ddim_sample_loop(dit.forward_with_cfg, x.shape, noise=x, clip_denoised=False, model_kwargs=kw))
+        loop, label = {"ddim": (diffusion.ddim_sample_loop, "DDIM"), "dpm": (diffusion.dpm_solver_sample_loop, "DPM-Solver++(2M)")}[a.sampler]
+        samples = timed(f"{label} loop, {a.steps} steps, CFG 6 (first call)",
+                        lambda: loop(dit.forward_with_cfg, x.shape, noise=x, clip_denoised=False, model_kwargs=kw))
         recon = timed("de-normalise + VAE decode", lambda: pipeline.latents_to_primitives(samples, vae, mean, std))
         recon[:, :, 1:4] = 1.2 * torch.rand_like(recon[:, :, 1:4]) - 0.6      # random networks: give the primitives a plausible layout
     normal = torch.tensor(a.normal, device=dev)
@@ -100,10 +103,11 @@ def main():
 
     def edit():
         return pipeline.redenoise_primitives(recon, vae, dit, diffusion, y, start_step=a.start_step, mode=a.mode, keep=keep,
-                                             generator=torch.Generator(device=dev).manual_seed(11), latent_mean=mean, latent_std=std)
+                                             generator=torch.Generator(device=dev).manual_seed(11), latent_mean=mean, latent_std=std,
+                                             sampler=a.sampler)
     edit_steps = a.start_step + 1 + (a.start_step if a.mode == "invert" else 0)
-    timed(f"redenoise_primitives, {edit_steps} DiT steps (first call)", edit)
-    out = timed(f"redenoise_primitives, {edit_steps} DiT steps", edit)
+    timed(f"redenoise_primitives, {a.sampler}, {edit_steps} DiT steps (first call)", edit)
+    out = timed(f"redenoise_primitives, {a.sampler}, {edit_steps} DiT steps", edit)
     if keep is not None:
         same = bool(torch.equal(out[keep], trip[keep]))
         moved = int((out[~keep] != trip[~keep]).any(-1).sum())

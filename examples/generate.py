@@ -5,9 +5,12 @@ inference.py:312-352 does it:
         -> PrimSDF lattice query (mesh-extraction input) + one ray-marched preview [+ GLB mesh with --mesh]
         [+ UV-mapped PBR GLB with --texmesh]
 
+--sampler dpm runs the loop with DPM-Solver++(2M) (diffusion/sampler.py: 10 to 15 steps in place of 25, e.g. --sampler dpm
+--steps 12); on synthetic weights that shows the loop's time, not its quality.
+
 There are no checkpoints offline: every network carries random weights, so the outputs are noise - the point is the
 data flow, the shapes and the per-stage timing.
-    python examples/generate.py [--steps 25] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
+    python examples/generate.py [--steps 25] [--sampler ddim|dpm] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
                                 [--texmesh OUT.glb [--texture-size 1024]] [--clean] [--decimate N]
 """
 import argparse
@@ -25,6 +28,8 @@ import __graft_entry__  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=25)
+    ap.add_argument("--sampler", choices=["ddim", "dpm"], default="ddim", help="dpm: DPM-Solver++(2M) over the same ddim<steps> "
+                    "grid, meant for 10 to 15 steps")
     ap.add_argument("--res", type=int, default=128, help="preview resolution")
     ap.add_argument("--lattice", type=int, default=96, help="SDF lattice resolution (the CLI uses 256)")
     ap.add_argument("--small", action="store_true", help="tiny networks (smoke run)")
@@ -75,15 +80,16 @@ def main():
         t0 = time.perf_counter()
         r = fn()
         torch.cuda.synchronize()
-        print(f"{name:34s} {1e3 * (time.perf_counter() - t0):9.2f} ms", flush=True)
+        print(f"{name:38s} {1e3 * (time.perf_counter() - t0):9.2f} ms", flush=True)
         return r
 
     image = torch.rand(1, 3, img, img, device=dev)
     y = timed("DINOv2 conditioner tokens", lambda: cond.conditioner_tokens(image))
     x = torch.randn(1, n_prims, 68).to(dev)
     kw = dict(y=y, cfg_scale=6.0, precision_dtype=torch.float16, enable_amp=True)
-    timed("DDIM loop (warm-up, 1st call)", lambda: diffusion.ddim_sample_loop(dit.forward_with_cfg, x.shape, noise=x, clip_denoised=False, model_kwargs=kw))
-    samples = timed(f"DDIM loop, {a.steps} steps, CFG 6", lambda: diffusion.ddim_sample_loop(dit.forward_with_cfg, x.shape, noise=x, clip_denoised=False, model_kwargs=kw))
+    loop, label = {"ddim": (diffusion.ddim_sample_loop, "DDIM"), "dpm": (diffusion.dpm_solver_sample_loop, "DPM-Solver++(2M)")}[a.sampler]
+    timed(f"{label} loop (warm-up, 1st call)", lambda: loop(dit.forward_with_cfg, x.shape, noise=x, clip_denoised=False, model_kwargs=kw))
+    samples = timed(f"{label} loop, {a.steps} steps, CFG 6", lambda: loop(dit.forward_with_cfg, x.shape, noise=x, clip_denoised=False, model_kwargs=kw))
     mean, std = [0.0] * 68, [1.0] * 68
     recon = timed("de-normalise + VAE decode", lambda: pipeline.latents_to_primitives(samples, vae, mean, std))
     # random networks produce arbitrary scales: give the primitives a plausible pose so that the last two stages have work
