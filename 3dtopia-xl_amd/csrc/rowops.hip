@@ -948,3 +948,39 @@ extern "C" int primx_latent_norm(const float* srt, const float* z, const float* 
     PRIMX_CHECK_LAUNCH("primx_latent_norm");
     return PRIMX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// One Adam step over n fp32 elements (torch.optim.Adam without amsgrad or weight decay; the refinement loop of fit.py), every
+// expression evaluated as written:
+//   m = m + w1 * (g - m);  v = v * beta2 + (w2 * g) * g;  p = p - ((lr / bc1) * m) / (sqrt(v) / sqrt(bc2) + eps)
+// w1 = 1 - beta1 and w2 = 1 - beta2 are taken in double from the double betas and rounded once, as torch rounds its Python
+// scalars (1 - 0.999f is 1.3e-5 off 0.001); bc1 = 1 - beta1^t and bc2 = 1 - beta2^t come from the caller the same way.
+__global__ void adam_step_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 int64_t n, float lr, float w1, float beta2, float w2, float eps, float bc1, float bc2,
+                                 int zero_grad) {
+#pragma clang fp contract(off)
+    const float step = lr / bc1, rbc2 = sqrtf(bc2);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float gi = g[i];
+        const float mi = m[i] + w1 * (gi - m[i]);
+        const float vi = v[i] * beta2 + (w2 * gi) * gi;
+        const float denom = sqrtf(vi) / rbc2 + eps;
+        p[i] = p[i] - (step * mi) / denom;
+        m[i] = mi;
+        v[i] = vi;
+        if (zero_grad) g[i] = 0.f;
+    }
+}
+
+extern "C" int primx_adam_step(float* param, float* grad, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
+                               float eps, float bc1, float bc2, int zero_grad, void* stream) {
+    PRIMX_REQUIRE(param && grad && m && v && n > 0, "primx_adam_step: bad argument");
+    PRIMX_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "primx_adam_step: betas must lie in [0, 1)");
+    PRIMX_REQUIRE(bc1 > 0.f && bc2 > 0.f, "primx_adam_step: the bias corrections 1 - beta^t must be positive");
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adam_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, n, lr,
+                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, bc1, bc2, zero_grad);
+    PRIMX_CHECK_LAUNCH("primx_adam_step");
+    return PRIMX_OK;
+}

@@ -4,7 +4,10 @@ The reference never released this step: `PrimSDF._init_param` is an empty `pass`
 here is the initialisation the 3DTopia-XL paper describes: sample candidate points uniformly on the surface, farthest-point-
 sample N of them as primitive centres, set each scale to the distance to the nearest other centre, and fill each primitive's
 S^3 payload with the mesh's signed distance, colour and material at `t_k + s_k * I`.  The short gradient refinement the paper
-runs afterwards is NOT built.
+runs afterwards is `refine_primitives` (`refine=N` of `mesh_to_primitives` / `PrimSDF.from_mesh`): full-batch Adam steps on the
+payload and, optionally, on scale and position, against the mesh's own field at a fixed seeded point set
+(`primx_primsdf_query_backward`, csrc/primsdf.hip; `primx_adam_step`, csrc/rowops.hip).  The paper's hyper-parameters are not in
+the reference tree: the defaults below are this project's choice, measured on the example torus (DESIGN.md "Refinement").
 
 Kernels (csrc/meshfield.hip, rules in include/primx_hip.h "Primitive fitting"): `primx_mesh_field_query` (brute force over
 the faces: exact point-triangle distance, generalized winding number, attributes at the closest point),
@@ -183,15 +186,83 @@ def _mesh_parts(mesh, dev):
     return v, f, attr.contiguous()
 
 
+REFINE_SCALE_FLOOR = 1e-4  # the scale is clamped to this after every step (fitted scales are positive; 0 would cover nothing)
+
+
+def refine_points(srt: torch.Tensor, samples_per_prim: int, seed: int = 0) -> torch.Tensor:
+    """[P * samples_per_prim, 3] fp32: pos + scale * U(-1, 1)^3 per primitive, the uniforms from a seeded CPU generator (the same
+    numbers on every device), the product and the sum as two fp32 operations."""
+    P = srt.shape[0]
+    u = torch.rand(P, int(samples_per_prim), 3, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32) * 2 - 1
+    u = u.to(srt.device)
+    return (srt[:, None, 1:4] + srt[:, None, 0:1] * u).reshape(-1, 3).contiguous()
+
+
+def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, samples_per_prim: int = 256, seed: int = 0,
+                      refine_srt: bool = False, weights=(1.0, 1.0, 1.0), lr_srt: Optional[float] = None, chunk: int = 1 << 20):
+    """`steps` full-batch Adam steps on recon [P, 4 + 6 S^3] (fp32, HIP device) against `field.query` (a `MeshField`, or anything
+    returning {'sdf' [n, 1], 'tex' [n, 3], 'mat' [n, 2]}) -> (recon', info).  `recon` itself is not modified.
+
+    The training set is fixed: `refine_points(recon[:, :4], samples_per_prim, seed)`, taken from the initial srt, with targets
+    from one `field.query` (the only host synchronisation here is that query's own; the loop has none).  Per step: the
+    training-mode query, loss = sum(diff^2 * coef / 2) with coef = 2 w / (n * channels) per group (= w_sdf mse(sdf) +
+    w_tex mse(tex) + w_mat mse(mat), on the clipped outputs), `primx_primsdf_query_backward` on gout = diff * coef, then
+    `primx_adam_step` (betas 0.9 / 0.999, eps 1e-8) on the payload with `lr` and, if `refine_srt`, on srt with `lr_srt`
+    (default lr / 100: an Adam step moves every element by about its rate, and a centre that drifts by a fraction of a voxel
+    without need costs more than the payload gains), after which the scale is clamped to
+    REFINE_SCALE_FLOOR.  `info`: 'loss' (the per-step losses BEFORE each step, read back once at the end), 'points',
+    'target'.  The gradient sums are atomic: the last bits differ from run to run."""
+    from . import primsdf
+    _need_cuda("refine_primitives", recon)
+    if recon.dim() != 2 or recon.dtype != torch.float32:
+        raise ValueError("recon must be fp32 [P, 4 + 6 S^3]")
+    P = recon.shape[0]
+    S = round(((recon.shape[1] - 4) / 6) ** (1.0 / 3.0))
+    if P == 0 or S < 2 or 4 + 6 * S ** 3 != recon.shape[1]:
+        raise ValueError(f"recon must be [P, 4 + 6 S^3] with P > 0 and S >= 2, got {tuple(recon.shape)}")
+    steps = int(steps)
+    if steps < 0 or samples_per_prim < 1:
+        raise ValueError("steps must be >= 0 and samples_per_prim >= 1")
+    lr_srt = 0.01 * lr if lr_srt is None else lr_srt
+    dev = recon.device
+    with torch.cuda.device(dev), torch.no_grad():
+        srt, feat = recon[:, :4].clone().contiguous(), recon[:, 4:].clone().contiguous()
+        pts = refine_points(srt, samples_per_prim, seed)
+        n = pts.shape[0]
+        parts = [field.query(pts[lo:lo + chunk]) for lo in range(0, n, chunk)]
+        target = torch.cat([torch.cat([q["sdf"], q["tex"], q["mat"]], 1) for q in parts]).float().contiguous()
+        w_sdf, w_tex, w_mat = (float(w) for w in weights)
+        coef = torch.tensor([2 * w_sdf / n] + [2 * w_tex / (3 * n)] * 3 + [2 * w_mat / (2 * n)] * 2, dtype=torch.float32).to(dev)
+        half_coef = coef * 0.5
+        lin = torch.linspace(-1, 1, S).to(dev)
+        losses = torch.zeros(max(steps, 1), dtype=torch.float32, device=dev)
+        gf, mf, vf = (torch.zeros_like(feat) for _ in range(3))
+        gs, ms, vs = (torch.zeros_like(srt) for _ in range(3)) if refine_srt else (None, None, None)
+        for t in range(1, steps + 1):
+            diff = primsdf._query_train(pts, srt, feat, lin, S) - target
+            losses[t - 1] = (diff * diff * half_coef).sum()
+            primsdf.query_backward(pts, srt, feat, diff * coef, S, gsrt=gs, gfeat=gf, want_srt=refine_srt)
+            ops.adam_step(feat, gf, mf, vf, t, lr, zero_grad=True)
+            if refine_srt:
+                ops.adam_step(srt, gs, ms, vs, t, lr_srt, zero_grad=True)
+                srt[:, 0].clamp_(min=REFINE_SCALE_FLOOR)
+        out = torch.cat([srt, feat], 1).contiguous()
+        loss = losses[:steps].cpu().tolist()                                  # the one read-back, after the loop
+    return out, {"loss": loss, "points": pts, "target": target, "steps": steps}
+
+
 def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candidates: Optional[int] = None, seed: int = 0,
-                       normalize: bool = True, extent: float = 0.9, device=None, chunk: int = 1 << 20):
+                       normalize: bool = True, extent: float = 0.9, device=None, chunk: int = 1 << 20, refine: int = 0,
+                       refine_kw: Optional[dict] = None):
     """mesh: a `mesh.TriMesh` or (v, f, albedo [V, 3], roughness [V], metallic [V]) -> (recon_param [P, 4 + 6 S^3], info).
 
     `candidates` (default 32 P) surface samples drawn with `seed`; P of them by farthest point sampling from candidate 0;
     scale = distance to the nearest other centre; payload in `PrimSDF.feat_param`'s layout [sdf | rgb | roughness, metallic],
     each [z][y][x], evaluated at pos + scale * local_grid; colours and materials clipped to [0, 1], the SDF raw
     (`primitives_to_latents` applies the x5).  `normalize`: see `normalize_vertices`.  `info` has the normalisation
-    (`center`, `scale`: v' = (v - center) * scale), the candidates (`candidates`, `candidate_face`) and the chosen ones (`idx`)."""
+    (`center`, `scale`: v' = (v - center) * scale), the candidates (`candidates`, `candidate_face`) and the chosen ones (`idx`).
+    `refine=N` > 0 follows the initialisation with N steps of `refine_primitives(recon, field, N, **refine_kw)` against the
+    normalised mesh's field (`info['refine']` is its info); 0 is the initialisation alone."""
     if device is None:
         v0 = mesh[0] if isinstance(mesh, (tuple, list)) else mesh.v
         device = v0.device if isinstance(v0, torch.Tensor) and v0.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -216,13 +287,18 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
         sdf = torch.cat([q["sdf"] for q in parts]).reshape(P, S ** 3)
         a = torch.cat([torch.cat([q["tex"], q["mat"]], 1) for q in parts]).reshape(P, S ** 3, N_ATTR)
         recon = torch.cat([nn[:, None], pos, sdf, a.transpose(1, 2).reshape(P, -1)], 1).contiguous()
+        rinfo = None
+        if int(refine) > 0:
+            recon, rinfo = refine_primitives(recon, field, int(refine), **{"chunk": chunk, **(refine_kw or {})})
     info = {"center": center, "scale": scale, "v": v, "f": f, "attr": attr, "candidates": cand, "candidate_face": cface, "idx": idx}
+    if rinfo is not None:
+        info["refine"] = rinfo
     return recon, info
 
 
 def primsdf_from_mesh(cls, mesh, num_prims: int = 2048, prim_shape: int = 8, return_info: bool = False, **kw):
     """`PrimSDF.from_mesh`: a module in eval mode on the mesh's device holding `mesh_to_primitives(mesh, ...)`, ready for
-    `query`, `mesh.extract_mesh` and `pipeline.primitives_to_latents` (through `recon_param`)."""
+    `query`, `mesh.extract_mesh` and `pipeline.primitives_to_latents` (through `recon_param`).  `refine=N` (in `kw`) refines."""
     recon, info = mesh_to_primitives(mesh, num_prims=num_prims, prim_shape=prim_shape, **kw)
     m = cls(num_prims=recon.shape[0], dim_feat=6, prim_shape=prim_shape)
     m.srt_param = torch.nn.Parameter(recon[:, :4].contiguous(), requires_grad=False)

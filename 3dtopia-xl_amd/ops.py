@@ -1030,3 +1030,21 @@ def silu_f32(x: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(x)
     check(_lib.load().primx_silu_f32(_dev(x, "x", torch.float32), out.data_ptr(), x.numel(), _stream()), "primx_silu_f32")
     return out
+
+
+def adam_step(param: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float = 1e-3,
+              beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, zero_grad: bool = False) -> None:
+    """Step number `step` (1, 2, ...) of torch.optim.Adam (no amsgrad, no weight decay) in place on fp32 `param`, `m`, `v`:
+    primx_adam_step.  The bias corrections 1 - beta^step are taken here in double; `zero_grad` clears `grad` in the same launch."""
+    n = param.numel()
+    for name, t in (("param", param), ("grad", grad), ("m", m), ("v", v)):
+        if t.numel() != n:
+            raise ValueError(f"{name} has {t.numel()} elements, param has {n}")
+    if step < 1:
+        raise ValueError("step counts from 1")
+    if n == 0:
+        return
+    check(_lib.load().primx_adam_step(_dev(param, "param", torch.float32), _dev(grad, "grad", torch.float32),
+                                      _dev(m, "m", torch.float32), _dev(v, "v", torch.float32), n, lr, beta1, beta2, eps,
+                                      1.0 - float(beta1) ** step, 1.0 - float(beta2) ** step, 1 if zero_grad else 0, _stream()),
+          "primx_adam_step")

@@ -19,7 +19,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
-from .fit import mesh_field, mesh_to_primitives          # noqa: F401  (fitting a user's mesh: fit.py)
+from .fit import mesh_field, mesh_to_primitives, refine_primitives  # noqa: F401  (fitting a user's mesh: fit.py)
 from .mesh import read_ply                               # noqa: F401
 
 

@@ -5,12 +5,13 @@
         -> PrimSDF -> extract_mesh -> PLY            [-> primitives_to_latents with --vae: the 68-channel tokens]
 
 Without --ply a coloured torus is written first and read back, so the run is end to end on a written PLY.  The fit is the
-initialisation the 3DTopia-XL paper describes; its gradient refinement is not built.  Without --vae the encoder carries
+initialisation the 3DTopia-XL paper describes; --refine N follows it with N steps of gradient refinement against the mesh's own
+field and reports the field error at the surface candidates before and after.  Without --vae the encoder carries
 random weights (the tokens are then noise: the point is the data flow and the per-stage timing).  (The file is not called
 tokenize.py: a script directory is searched for modules first, and that name would replace the standard library's `tokenize`
 for every script in examples/.)
 
-    python examples/tokenize_mesh.py [--ply IN.ply] [--out OUT.ply] [--prims 2048] [--resolution 256] [--vae VAE.pt] [--denoised OUT.pt]
+    python examples/tokenize_mesh.py [--ply IN.ply] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--vae VAE.pt] [--denoised OUT.pt]
 """
 import argparse
 import math
@@ -45,6 +46,7 @@ def main():
     ap.add_argument("--out", default="tokenized.ply", help="the mesh extracted from the fitted primitives")
     ap.add_argument("--denoised", default=None, help="also save the primitives as a denoised.pt")
     ap.add_argument("--prims", type=int, default=2048)
+    ap.add_argument("--refine", type=int, default=0, help="refinement steps after the initialisation (fit.refine_primitives)")
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--vae", default=None, help="VAE checkpoint (.pt with 'model_state_dict'); random weights when absent")
@@ -77,14 +79,29 @@ def main():
     recon, info = timed("mesh_to_primitives", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed))
     print(f"  recon_param {tuple(recon.shape)}  scale {float(recon[:, 0].min()):.4f} .. {float(recon[:, 0].max()):.4f}  "
           f"normalised by x{float(info['scale']):.4f}")
-    field = PrimSDF(num_prims=recon.shape[0], dim_feat=6, prim_shape=8)
-    field.srt_param = torch.nn.Parameter(recon[:, :4].contiguous(), requires_grad=False)
-    field.feat_param = torch.nn.Parameter(recon[:, 4:].contiguous(), requires_grad=False)
-    field = field.to(dev).eval()
-    # how well the primitives hold the mesh: the fitted field at the surface candidates, where the mesh's own SDF is 0
-    with torch.no_grad():
-        s = field(info["candidates"])["sdf"][:, 0]
-    print(f"  fitted |sdf| at the {s.shape[0]} surface candidates: mean {float(s.abs().mean()):.2e}  max {float(s.abs().max()):.2e}")
+
+    def as_field(r):
+        m = PrimSDF(num_prims=r.shape[0], dim_feat=6, prim_shape=8)
+        m.srt_param = torch.nn.Parameter(r[:, :4].contiguous(), requires_grad=False)
+        m.feat_param = torch.nn.Parameter(r[:, 4:].contiguous(), requires_grad=False)
+        return m.to(dev).eval()
+
+    def report(m, what):
+        # how well the primitives hold the mesh: the fitted field at the surface candidates, where the mesh's own SDF is 0
+        with torch.no_grad():
+            s = m(info["candidates"])["sdf"][:, 0]
+        print(f"  {what} |sdf| at the {s.shape[0]} surface candidates: mean {float(s.abs().mean()):.2e}  max {float(s.abs().max()):.2e}")
+
+    field = as_field(recon)
+    report(field, "fitted")
+    if a.refine > 0:
+        from topia_xl_amd import fit
+        target = fit.MeshField(info["v"], info["f"], info["attr"])
+        fit.refine_primitives(recon, target, 1)                                       # (first call: loads the kernels)
+        recon, rinfo = timed(f"refine_primitives, {a.refine} steps", lambda: fit.refine_primitives(recon, target, a.refine))
+        print(f"  loss {rinfo['loss'][0]:.3e} -> {rinfo['loss'][-1]:.3e}")
+        field = as_field(recon)
+        report(field, "refined")
     out = timed(f"extract_mesh {a.resolution}^3", lambda: M.extract_mesh(field, resolution=a.resolution))
     print(f"  V = {out.v.shape[0]}  F = {out.f.shape[0]}")
     out.write_ply(a.out)

@@ -83,7 +83,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 33
+#define PRIMX_ABI_VERSION 34
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -601,6 +601,40 @@ int primx_enc_head(const void* in, const void* Wk, int Kpad, const float* bias, 
  * fill of points no primitive covers (primsdf.py:78-100). */
 int primx_primsdf_query(const float* pts, const float* srt, const float* feat, const float* lin, float* out, int n, int P,
                         int S, int C, int eval_fill, void* stream);
+
+/* Backward of the training-mode query (eval_fill = 0; there is no fill here: a point no primitive covers contributes
+ * nothing).  ABI 34.  pts, srt, feat as above; gout [n, C] = the gradient of a scalar loss with respect to the forward's
+ * returned columns (after the clip).  The kernel ADDS d loss / d srt into gsrt [P, 4] and d loss / d feat into
+ * gfeat [P, C * S^3], both fp32; the caller zeroes them.  Either may be null to skip that gradient (not both).  Same domain
+ * as the forward: 2 <= S <= 32, 1 <= C <= 6.  Per point x and primitive k, with d = x - pos_k, s = scale_k, u = d / s,
+ * half = (S - 1) / 2:
+ *   - covering test: the forward's cull max_a |d_a| < |s| and its w_k > 0 test, the same expressions, so both kernels agree
+ *     on which primitives cover a point;
+ *   - forward quantities: w_k = 1 - max_a |d_a| / |s|; inv = 1 / (sum_k w_k + 1e-6); sigma_kc = the trilinear sample in
+ *     the forward's cell min(floor(f), S - 2) clamped at 0, f = (u + 1) half; o_c = inv sum_k w_k sigma_kc;
+ *   - clip: g_0 = gout_0; for c >= 1, g_c = gout_c where 0 <= o_c <= 1 (inclusive, as torch.clip differentiates), else 0;
+ *   - payload: gfeat_k[c, corner] += g_c w_k inv tau_corner for the 8 trilinear corner weights tau of the forward's cell;
+ *   - weight path: a_k = inv sum_c g_c (sigma_kc - o_c);
+ *   - sample path: b_ka = w_k inv half sum_c g_c d sigma_kc / d f_a, the trilinear derivative inside the forward's cell;
+ *   - argmax: j = the axis of the maximum |d_a|, the first of equals in x, y, z order (this project's convention; torch's
+ *     amax splits the gradient evenly among ties); sign(0) = 0;
+ *   - position: gsrt_k[1 + a] += -b_ka / s + [a == j] a_k sign(d_j) / |s|;
+ *   - scale:    gsrt_k[0]     += a_k |d_j| sign(s) / s^2 - sum_a b_ka d_a / s^2.
+ * The four gsrt terms of a (point, primitive) pair are summed in registers; every add is a global fp32 atomic add, so the sums
+ * depend on the arrival order and the results are NOT bitwise reproducible from run to run (one or two contributions per
+ * address are: fp32 addition commutes).  Nothing outside gsrt / gfeat is written; no workspace, no host synchronisation. */
+int primx_primsdf_query_backward(const float* pts, const float* srt, const float* feat, const float* gout, float* gsrt,
+                                 float* gfeat, int n, int P, int S, int C, void* stream);
+
+/* One Adam step over n fp32 elements, in place on param, m, v (torch.optim.Adam without amsgrad and weight decay), every
+ * expression as written and uncontracted, division and square root correctly rounded:
+ *   m = m + w1 (g - m);  v = v fl(beta2) + (w2 g) g;  param = param - ((lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps)
+ * w1 = fl(1 - beta1), w2 = fl(1 - beta2): the betas are doubles, the differences are taken in double and rounded to fp32 once
+ * (as torch rounds its Python scalars).  bc1 = 1 - beta1^t and bc2 = 1 - beta2^t are computed by the caller in double and
+ * passed as floats (both > 0).
+ * zero_grad != 0 stores 0 into grad after it was read, so a loop needs no memset.  ABI 34. */
+int primx_adam_step(float* param, float* grad, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+                    float bc1, float bc2, int zero_grad, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Mesh extraction (inference.py:86-125, extract_texmesh up to the texture bake).  ABI 27.
