@@ -26,6 +26,7 @@
 // over channels-last [P, S^3, Cin] activations: k = tap * Cin + ci, row m = (p, voxel); out-of-volume taps
 // and any K tail read a 16-byte zero block instead of branching.
 #include <stdio.h>
+#include <string.h>
 #include <algorithm>
 #include <type_traits>
 
@@ -1627,46 +1628,37 @@ __global__ __launch_bounds__(512, 2) void gemm288q_pair_kernel(PRIMX_GEMM_PARAMS
 // DMA unit's queue or waits for its staged slice, and nobody covers it in the epilogue.  Removed; measurements, timelines and the
 // inline-asm-MFMA hazard found on the way: profiles/r4_experiments.txt sections 2 - 3, DESIGN_LOG.md section 10.)
 
-static const bool g_no_big = [] {   // PRIMX_GEMM_NOBIG=1 disables the 256x288 tile (A/B measurements)
-    const char* e = getenv("PRIMX_GEMM_NOBIG");
+// ---- The switches of the GEMM dispatch (A/B measurements): every one is read ONCE, when the library loads, by one of three rules.
+static bool env_is_1(const char* name) {           // set, and the value starts with '1'
+    const char* e = getenv(name);
     return e && e[0] == '1';
-}();
-
-static const bool g_loader = [] {   // PRIMX_GEMM_LOADER=0: the 128x144 kernel without loader waves (gemm144_dma_kernel) everywhere
-    const char* e = getenv("PRIMX_GEMM_LOADER");
+}
+static bool env_not_0(const char* name) {          // on unless the value starts with '0'
+    const char* e = getenv(name);
     return !(e && e[0] == '0');
-}();
+}
+static int env_int(const char* name, int dflt) {   // atoi of the value, `dflt` when unset
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static const bool g_no_big = env_is_1("PRIMX_GEMM_NOBIG");                  // =1 disables the 256x288 tile
+static const bool g_loader = env_not_0("PRIMX_GEMM_LOADER");                // =0: the 128x144 kernel without loader waves (gemm144_dma_kernel) everywhere
+// (224: one launch fills the chip; 112 when two half-batch streams run side by side)
+static const int g_big_min = env_int("PRIMX_GEMM_BIG_MIN", 224);            // fewest 256x288 workgroups for which the dense-output epilogues take the big tile
+static const int g_big_heads_min = env_int("PRIMX_GEMM_BIGHEADS_MIN", 160); // fewest 256x288 workgroups for which the heads epilogue takes the big tile (0 = never)
+static const bool g_xcd2d = env_not_0("PRIMX_GEMM_XCD2D");                  // =0: whole tile rows per XCD in the 256x288 kernel
+static const bool g_ln_fuse = env_not_0("PRIMX_LN_FUSE");                   // =0: primx_linear_gate_residual_ln always takes the two-launch route
+// (bit 0 light release | acquire kind << 1 | per-workgroup arrival 8 | sleep << 4, see the tail of gemm144l_dma_kernel; 41: same-XCD release -
+// stores acknowledged by the shared L2 -, agent-scope acquire, one arrival per workgroup)
+static const int g_ln_mode = env_int("PRIMX_LN_MODE", 1 | (0 << 1) | 8 | (2 << 4));   // fences and arrival protocol of the LayerNorm in the GEMM's tail
+static const int g_ln_maxgrid = env_int("PRIMX_LN_FUSE_MAXGRID", 2048);     // largest grid of a launch with the LayerNorm in its tail
+static const bool g_gemm_prof_on = env_int("PRIMX_GEMM_PROF", 0) != 0;      // =1: synchronous launches + per-workgroup timeline print (8-wave kernels)
+static const bool g_kt32 = env_int("PRIMX_GEMM_KT32", 0) != 0;              // =1: the 256x288 kernel on its round 1 - 5 ring of 32-wide slices (64-byte requests) for every K
+static const int g_kt64_min = env_int("PRIMX_GEMM_KT64_MIN", -1);           // fewest 256x288 workgroups for which the dense-output epilogues take 128-byte row segments (-1: the rule of kt64_ring)
+static const bool g_heads_kt64 = env_int("PRIMX_GEMM_HEADS_KT32", 0) == 0;  // =1: the heads epilogues of the 256x288 kernel on the ring of 32-wide slices (rounds 1 - 6a)
+static const bool g_no_gemv = env_is_1("PRIMX_GEMM_NOGEMV");                // =1: few-row Linear (M <= 8) on the MFMA tiles instead of gemv16_kernel
+static const bool g_f32out_tile144 = env_not_0("PRIMX_F32OUT_TILE144");     // =0: primx_linear_f32out never on the loader-wave 128x144 kernel
 
-static const int g_big_min = [] {   // PRIMX_GEMM_BIG_MIN: fewest 256x288 workgroups for which the dense-output epilogues take the big tile
-    const char* e = getenv("PRIMX_GEMM_BIG_MIN");   // (224: one launch fills the chip; 112 when two half-batch streams run side by side)
-    return e ? atoi(e) : 224;
-}();
-
-static const int g_big_heads_min = [] {   // fewest 256x288 workgroups for which the heads epilogue takes the big tile
-    const char* e = getenv("PRIMX_GEMM_BIGHEADS_MIN");
-    return e ? atoi(e) : 160;
-}();
-
-static const bool g_xcd2d = [] {   // PRIMX_GEMM_XCD2D=0: whole tile rows per XCD in the 256x288 kernel (A/B measurements)
-    const char* e = getenv("PRIMX_GEMM_XCD2D");
-    return !(e && e[0] == '0');
-}();
-
-// LayerNorm in the tail of the gate-residual GEMM (primx_linear_gate_residual_ln): PRIMX_LN_FUSE=0 always takes the two-launch
-// route; PRIMX_LN_MODE selects the fences and the arrival protocol (A/B measurements);
-// PRIMX_LN_FUSE_MAXGRID bounds the grid of a fused launch.
-static const bool g_ln_fuse = [] {
-    const char* e = getenv("PRIMX_LN_FUSE");
-    return !(e && e[0] == '0');
-}();
-static const int g_ln_mode = [] {   // PRIMX_LN_MODE: see the tail of gemm144l_dma_kernel (bit 0 light release | acquire kind << 1 | per-workgroup arrival 8 | sleep << 4)
-    const char* e = getenv("PRIMX_LN_MODE");
-    return e ? atoi(e) : (1 | (0 << 1) | 8 | (2 << 4));   // 41: same-XCD release (stores acknowledged by the shared L2), agent-scope acquire, one arrival per workgroup
-}();
-static const int g_ln_maxgrid = [] {
-    const char* e = getenv("PRIMX_LN_FUSE_MAXGRID");
-    return e ? atoi(e) : 2048;
-}();
 // The fused route's same-XCD fences rest on the workgroup -> XCD mapping that xcd_remap assumes everywhere (workgroup id mod 8 =
 // XCD): checked ONCE per device by a probe launch (every workgroup reports the XCC it runs on) before the first fused launch; a
 // device that maps differently (another partition mode, fewer XCDs) takes the two-launch route.
@@ -1696,11 +1688,6 @@ static bool xcd_mapping_ok(hipStream_t st) {
 }
 thread_local bool g_ln_fused = false;   // did the last launch144_dma on this thread run the LayerNorm in the GEMM's tail?
 
-static const bool g_gemm_prof_on = [] {   // PRIMX_GEMM_PROF=1: synchronous launches + per-workgroup timeline print (8-wave kernels)
-    const char* e = getenv("PRIMX_GEMM_PROF");
-    return e && atoi(e) != 0;
-}();
-
 // The kernel instantiation the last GEMM entry point called on this thread selected, spelled as rocprofv3 prints it
 // (primx_last_gemm_kernel(), include/primx_hip.h): bench.py tags its per-launch timings with what the C side actually
 // launched instead of a Python restatement of the dispatch rules below.
@@ -1721,59 +1708,42 @@ static int xcd_pack(int gm, int mtb, int ntb, bool row_major) {
 }
 
 
-static const bool g_kt32 = [] {   // PRIMX_GEMM_KT32=1: the 256x288 kernel on its round 1 - 5 ring of 32-wide slices (64-byte requests) for every K
-    const char* e = getenv("PRIMX_GEMM_KT32");
-    return e && atoi(e) != 0;
-}();
+constexpr bool epi_is_heads(int epi) { return epi == EPI_HEADS || epi == EPI_HEADS_FOLD; }
+constexpr bool epi_is_fold(int epi) { return epi == EPI_GATE_RESIDUAL_FOLD || epi == EPI_HEADS_FOLD || epi == EPI_LINEAR_FOLD; }
+constexpr bool epi_is_dense(int epi) {
+    return epi == EPI_LINEAR || epi == EPI_GATE_RESIDUAL || epi == EPI_GATE_RESIDUAL_FOLD || epi == EPI_LINEAR_FOLD || epi == EPI_RES;
+}
 
-static const int g_kt64_min = [] {   // PRIMX_GEMM_KT64_MIN: fewest 256x288 workgroups for which the dense-output epilogues take 128-byte row segments
-    const char* e = getenv("PRIMX_GEMM_KT64_MIN");
-    return e ? atoi(e) : -1;   // (-1: the rule of launch288q)
-}();
-
-// Which ring: 128-byte row segments (KT = 64) for the dense-output epilogues of launches with more than one round of workgroups -
-// measured (profiles/r6_kt64_experiments.txt, same box): fc1 + GELU at T = 32768 466 -> 437 us, proj 145 -> 134, fc2 371 -> 345; at
-// ONE round (qkv at T = 4096: 192 workgroups) the two-stage ring's longer first wait costs more than the request rate gives (44.5 ->
-// 46.5 us), and the heads epilogues neither gain (T = 16384 qkv 137 vs 137 us) nor fit the registers (the compiler spills 7 - 29
-// dwords next to their two main loops): both keep the 32-wide ring.  (KT = 64 addresses its operands by 32-bit byte offsets.)
-static const bool g_heads_kt64 = [] {   // PRIMX_GEMM_HEADS_KT32=1: the heads epilogues of the 256x288 kernel on the ring of 32-wide slices (rounds 1 - 6a)
-    const char* e = getenv("PRIMX_GEMM_HEADS_KT32");
-    return !(e && atoi(e) != 0);
-}();
-
-// The heads epilogues on the 128-byte ring (end of round 6): with the rolling fragment window of gemm288q_body.inc they fit the registers
-// (no scratch), and their k-loop leaves the request-bound regime like the dense epilogues' did.
+// Which ring of the 256 x 288 kernel (`wgs` workgroups): 128-byte row segments (KT = 64) for the dense-output epilogues of launches with
+// more than one round of workgroups - measured (profiles/r6_kt64_experiments.txt, same box): fc1 + GELU at T = 32768 466 -> 437 us,
+// proj 145 -> 134, fc2 371 -> 345; at ONE round (qkv at T = 4096: 192 workgroups) the two-stage ring's longer first wait costs more than
+// the request rate gives (44.5 -> 46.5 us).  The heads epilogues take it from K = 128 on (end of round 6): with the rolling fragment
+// window of gemm288q_body.inc they fit the registers (no scratch), and their k-loop leaves the request-bound regime like the dense
+// epilogues' did.
 template <int DT>
-static bool heads_kt64(const GemmArgs<DT>& x) {
-    return g_heads_kt64 && !g_kt32 && x.K % 64 == 0 && x.K >= 128 && (int64_t)x.M * x.K < (1ll << 31) && (int64_t)x.N * x.K < (1ll << 31);
+static bool kt64_ring(const GemmArgs<DT>& x, int epi, int wgs) {
+    if (g_kt32 || x.K % 64 != 0) return false;
+    if ((int64_t)x.M * x.K >= (1ll << 31) || (int64_t)x.N * x.K >= (1ll << 31)) return false;   // (KT = 64 addresses its operands by 32-bit byte offsets)
+    if (epi_is_heads(epi)) return g_heads_kt64 && x.K >= 128;
+    if (!epi_is_dense(epi)) return false;
+    const bool full = epi != EPI_GATE_RESIDUAL || (x.M % 256 == 0 && x.rows_per_batch % 256 == 0);   // (its pipelined epilogue: no ragged tile, one gate row per tile)
+    // (default: the Linear epilogues always - fc1 at T = 4096, ONE round of 256 workgroups, 50.5 -> 45.0 us in the step against the
+    //  two-pass kernel once this kernel carries the weight prefetch; the read-modify-write epilogues from two rounds on)
+    const int kt64_min = g_kt64_min >= 0 ? g_kt64_min : (epi == EPI_LINEAR || epi == EPI_LINEAR_FOLD) ? 1 : 257;
+    return full && wgs >= kt64_min;
 }
 
 template <int DT, int EPI>
 static void launch288q(const GemmArgs<DT>& x, dim3 grid, hipStream_t st) {
-    constexpr bool DENSE = EPI == EPI_LINEAR || EPI == EPI_GATE_RESIDUAL || EPI == EPI_GATE_RESIDUAL_FOLD || EPI == EPI_LINEAR_FOLD ||
-                           EPI == EPI_RES;
-    if constexpr (DENSE) {
-        const bool full = EPI != EPI_GATE_RESIDUAL || (x.M % 256 == 0 && x.rows_per_batch % 256 == 0);   // (its pipelined epilogue: no ragged tile, one gate row per tile)
-        // (default: the Linear epilogues always - fc1 at T = 4096, ONE round of 256 workgroups, 50.5 -> 45.0 us in the step against the
-        //  two-pass kernel once this kernel carries the weight prefetch; the read-modify-write epilogues from two rounds on)
-        const int kt64_min = g_kt64_min >= 0 ? g_kt64_min : (EPI == EPI_LINEAR || EPI == EPI_LINEAR_FOLD) ? 1 : 257;
-        if (x.K % 64 == 0 && !g_kt32 && full && (int)grid.x >= kt64_min && (int64_t)x.M * x.K < (1ll << 31) && (int64_t)x.N * x.K < (1ll << 31)) {
+    if constexpr (epi_is_dense(EPI) || epi_is_heads(EPI)) {   // (the epilogues the 128-byte ring is built for)
+        if (kt64_ring<DT>(x, EPI, (int)grid.x)) {
             PRIMX_NOTE_KERNEL("gemm288q_dma_kernel<%d, %d, 64>", DT, EPI);
             hipLaunchKernelGGL((gemm288q_dma_kernel<DT, EPI, 64>), grid, dim3(512), 0, st, PRIMX_GEMM_PASS(x));
             return;
         }
     }
-    if constexpr (EPI == EPI_HEADS || EPI == EPI_HEADS_FOLD) {
-        if (heads_kt64<DT>(x)) {
-            PRIMX_NOTE_KERNEL("gemm288q_dma_kernel<%d, %d, 64>", DT, EPI);
-            hipLaunchKernelGGL((gemm288q_dma_kernel<DT, EPI, 64>), grid, dim3(512), 0, st, PRIMX_GEMM_PASS(x));
-            return;
-        }
-    }
-    {
-        PRIMX_NOTE_KERNEL("gemm288q_dma_kernel<%d, %d, 32>", DT, EPI);
-        hipLaunchKernelGGL((gemm288q_dma_kernel<DT, EPI, 32>), grid, dim3(512), 0, st, PRIMX_GEMM_PASS(x));
-    }
+    PRIMX_NOTE_KERNEL("gemm288q_dma_kernel<%d, %d, 32>", DT, EPI);
+    hipLaunchKernelGGL((gemm288q_dma_kernel<DT, EPI, 32>), grid, dim3(512), 0, st, PRIMX_GEMM_PASS(x));
 }
 
 // XCD block shape of a 256 x 288 launch (packed for xcd_tile2d; 0 = whole tile rows per XCD): minimise (A bytes x column groups + W bytes
@@ -1796,81 +1766,72 @@ static int big_xcd_gm(const GemmArgs<DT>& a, bool heads) {
     return g > 0 ? xcd_pack(g, mtb, ntb, heads) : g;
 }
 
-template <int DT, int EPI, int BIG = 0>
-void launch144_dma(const GemmArgs<DT>& a, int mt, hipStream_t st) {
-    const dim3 grid(BIG ? ((a.M + 255) / 256) * (a.N / 288) : mt * (a.N / 144));
-    GemmArgs<DT> a2 = a;
-    a2.ln_light = g_ln_mode;
-    if (BIG) a2.xcd_gm = big_xcd_gm<DT>(a, EPI == EPI_HEADS || EPI == EPI_HEADS_FOLD);
-    constexpr bool FOLD_EPI = EPI == EPI_GATE_RESIDUAL_FOLD || EPI == EPI_HEADS_FOLD || EPI == EPI_LINEAR_FOLD;
-    // loader-wave kernel: the row-major epilogues (heads: token-major segments whose tiles stay inside one segment)
-    bool loader_ok = !BIG && (EPI == EPI_LINEAR || EPI == EPI_GATE_RESIDUAL || EPI == EPI_GATE_RESIDUAL_FOLD || EPI == EPI_LINEAR_FOLD);
-    if (!BIG && (EPI == EPI_HEADS || EPI == EPI_HEADS_FOLD) && a.heads > 0) {
-        const int per = a.heads * a.dh;
-        loader_ok = per % 144 == 0 && a.dh >= 48 && a.dh % 4 == 0 && a.rows_per_batch >= 128;
-        for (int sgi = 0; sgi < a.n_seg; ++sgi) loader_ok = loader_ok && a.kind[sgi] != PRIMX_HEADS_VT;
-    }
-    auto go = [&](const GemmArgs<DT>& x) {
-        // the LayerNorm-fold epilogues exist in exactly one kernel per tile shape (launch_fold checked the shape)
-        if constexpr (FOLD_EPI) {
-            if constexpr (BIG) {
-                launch288q<DT, EPI>(x, grid, st);
-            } else {
-                PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI);
-                hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI>), grid, dim3(640), 0, st, PRIMX_GEMM_PASS(x));
-            }
-            return;
-        } else {
-        if (BIG) {
-            launch288q<DT, EPI>(x, grid, st);
-        } else if (g_loader && loader_ok) {
-            if constexpr (EPI == EPI_GATE_RESIDUAL) {
-                // LayerNorm of the updated rows in the kernel's tail: N = 1152 (nine 128-column chunks per half-wave row), 8-byte
-                // aligned modulation vectors, and every row block's column tiles on ONE XCD with consecutive ids (mt % 8 == 0:
-                // xcd_remap hands each XCD mt / 8 whole blocks) - see the kernel for why the in-kernel wait is safe then
-                const int nt = x.N / 144;
-                if (x.ln_out && x.sync && g_ln_fuse && x.N == 1152 && mt % 8 == 0 && (int)grid.x <= g_ln_maxgrid && nt * 8 <= 128 &&
-                    (((uintptr_t)x.ln_shift | (uintptr_t)x.ln_scale | (uintptr_t)x.ln_out) & 7) == 0 && x.ln_mod_stride % 4 == 0 &&
-                    xcd_mapping_ok(st)) {
-                    PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI_GATE_RESIDUAL_LN);
-                    hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI_GATE_RESIDUAL_LN>), grid, dim3(640), 0, st, PRIMX_GEMM_PASS(x));
-                    g_ln_fused = true;
-                    return;
-                }
-            }
-            if constexpr (EPI == EPI_LINEAR || EPI == EPI_GATE_RESIDUAL || EPI == EPI_HEADS) {
-                PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI);
-                hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI>), grid, dim3(640), 0, st, PRIMX_GEMM_PASS(x));
-            }
-        } else {
-            PRIMX_NOTE_KERNEL("gemm144_dma_kernel<%d, %d>", DT, EPI);
-            hipLaunchKernelGGL((gemm144_dma_kernel<DT, EPI>), grid, dim3(512), 0, st, PRIMX_GEMM_PASS(x));
-        }
-        }
-    };
-    if (!g_gemm_prof_on) {
-        go(a2);
-        return;
-    }
-    GemmArgs<DT> b = a2;
-    b.prof = 1;
-    unsigned long long z[12] = {~0ull, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, r[12];
+// ---- The tile rules, each stated once.
+// Dense-output epilogues on the 256 x 288 tile: only where same-box A/B showed a win - enough workgroups to fill the chip (fc1 at
+// T = 4096: exactly 256; every large-batch GEMM).
+static bool big_dense_ok(int M, int N) { return !g_no_big && N % 288 == 0 && ((M + 255) / 256) * (N / 288) >= g_big_min; }
+
+// Heads epilogue on the 256 x 288 tile (LDS-staged scatter, gemm288q only) - the SHAPE: tiles must cover whole heads of one segment
+// and one batch entry (dh >= 32: the epilogue finds the head of a column with at most 8 compare-subtract steps, 288 / dh <= 9 heads
+// per tile).
+template <int DT>
+static bool big_heads_shape(const GemmArgs<DT>& a) {
+    const int per = a.heads * a.dh;
+    return !g_no_big && g_big_heads_min > 0 && a.heads > 0 && a.N % 288 == 0 && per % 288 == 0 && 288 % a.dh == 0 && a.dh % 8 == 0 &&
+           a.dh >= 32 && a.rows_per_batch % 256 == 0;
+}
+template <int DT>
+static int big_heads_wgs(const GemmArgs<DT>& a) { return (a.M / 256) * (a.N / 288); }
+// ... and with the workgroup threshold: it already pays at 192 workgroups (qkv at T = 4096: 75 % of the CUs, one round instead of three
+// rounds of 128x144 tiles); PRIMX_GEMM_BIGHEADS_MIN moves the threshold (0 = never).
+template <int DT>
+static bool big_heads_ok(const GemmArgs<DT>& a) { return big_heads_shape<DT>(a) && big_heads_wgs<DT>(a) >= g_big_heads_min; }
+
+// Heads epilogue on the loader-wave 128 x 144 kernel: token-major segments whose tiles stay inside one segment
+template <int DT>
+static bool loader_heads_ok(const GemmArgs<DT>& a) {
+    const int per = a.heads * a.dh;
+    bool ok = per % 144 == 0 && a.dh >= 48 && a.dh % 4 == 0 && a.rows_per_batch >= 128;
+    for (int s = 0; s < a.n_seg; ++s) ok = ok && a.kind[s] != PRIMX_HEADS_VT;
+    return ok;
+}
+
+// LayerNorm of the updated rows in the tail of the gate-residual kernel: N = 1152 (nine 128-column chunks per half-wave row), 8-byte
+// aligned modulation vectors, and every row block's column tiles on ONE XCD with consecutive ids (mt % 8 == 0: xcd_remap hands each XCD
+// mt / 8 whole blocks) - see gemm144l_dma_kernel for why the in-kernel wait is safe then
+template <int DT>
+static bool ln_tail_ok(const GemmArgs<DT>& x, int mt, int wgs, hipStream_t st) {
+    const int nt = x.N / 144;
+    return x.ln_out && x.sync && g_ln_fuse && x.N == 1152 && mt % 8 == 0 && wgs <= g_ln_maxgrid && nt * 8 <= 128 &&
+           (((uintptr_t)x.ln_shift | (uintptr_t)x.ln_scale | (uintptr_t)x.ln_out) & 7) == 0 && x.ln_mod_stride % 4 == 0 &&
+           xcd_mapping_ok(st);
+}
+
+// ---- PRIMX_GEMM_PROF=1: the timeline of one launch144_dma launch.  gemm_prof_begin in front of the launch, gemm_prof_report behind
+// it: waits for the launch and prints what its workgroups stamped, under the kernel name PRIMX_NOTE_KERNEL recorded.
+template <int DT>
+static void gemm_prof_begin(GemmArgs<DT>& x, hipEvent_t& e0, hipEvent_t& e1, hipStream_t st) {
+    x.prof = 1;
+    const unsigned long long z[12] = {~0ull, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_prof), z, sizeof(z));
-    hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, st);
-    go(b);
+}
+template <int DT>
+static void gemm_prof_report(const GemmArgs<DT>& a, int epi, hipEvent_t e0, hipEvent_t e1, hipStream_t st) {
+    unsigned long long r[12];
+    const char* const name = g_last_gemm_kernel;      // "gemm288q_dma_kernel<1, 0, 64>": printed up to "_kernel"
+    const char* const name_end = strstr(name, "_kernel");
     (void)hipEventRecord(e1, st);
     (void)hipEventSynchronize(e1);
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipMemcpyFromSymbol(r, HIP_SYMBOL(g_gemm_prof), sizeof(r));
     const double n = r[5] ? (double)r[5] : 1.0;
-    fprintf(stderr, "%s<%d,%d> M=%d N=%d K=%d: %llu workgroups, events %.1f us, first start -> last end %.1f us, mean start offset "
+    fprintf(stderr, "%.*s<%d,%d> M=%d N=%d K=%d: %llu workgroups, events %.1f us, first start -> last end %.1f us, mean start offset "
                     "%.1f us, shader clock %.2f GHz (core cycles / 100 MHz ticks per workgroup); per workgroup (core cycles): entry->tile0 %.0f | main loop "
                     "%.0f | epilogue %.0f (LDS staging %.0f, read+store issue %.0f)\n",
-            BIG ? "gemm288q_dma"
-                : (FOLD_EPI || (g_loader && loader_ok)) ? "gemm144l_dma" : "gemm144_dma", DT, EPI, a.M, a.N, a.K,
+            name_end ? (int)(name_end - name) : (int)strlen(name), name, DT, epi, a.M, a.N, a.K,
             r[5], ms * 1e3, (r[1] - r[0]) * 0.01, (r[6] / n - (double)r[0]) * 0.01, r[8] ? (double)r[9] / (double)r[8] * 0.1 : 0.0,
             r[2] / n, r[3] / n, r[4] / n, (r[7] >> 32) / n,
             (r[7] & 0xffffffffull) / n);
@@ -1911,6 +1872,44 @@ void launch144_dma(const GemmArgs<DT>& a, int mt, hipStream_t st) {
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
 }
 
+// One launch of an LDS-DMA kernel: the 256 x 288 tile (BIG) or the 128 x 144 tile, with loader waves where that kernel has the
+// epilogue and the layout fits it.  (The `if constexpr` inside a branch keeps a kernel from being instantiated with an epilogue it
+// does not have; the branch is never taken then.)
+template <int DT, int EPI, int BIG = 0>
+void launch144_dma(const GemmArgs<DT>& a, int mt, hipStream_t st) {
+    const dim3 grid(BIG ? ((a.M + 255) / 256) * (a.N / 288) : mt * (a.N / 144));
+    GemmArgs<DT> x = a;
+    x.ln_light = g_ln_mode;
+    if (BIG) x.xcd_gm = big_xcd_gm<DT>(a, epi_is_heads(EPI));
+    // gemm144l_dma_kernel: the only 128 x 144 kernel of the fold epilogues (launch_fold checked the shape); the row-major epilogues;
+    // the heads epilogue where the layout allows
+    constexpr bool FOLD_EPI = epi_is_fold(EPI), LOADER_EPI = EPI == EPI_LINEAR || EPI == EPI_GATE_RESIDUAL || EPI == EPI_HEADS;
+    const bool loader = FOLD_EPI || (LOADER_EPI && g_loader && (EPI != EPI_HEADS || (a.heads > 0 && loader_heads_ok<DT>(a))));
+    const bool ln_tail = !BIG && EPI == EPI_GATE_RESIDUAL && loader && ln_tail_ok<DT>(x, mt, (int)grid.x, st);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (g_gemm_prof_on) gemm_prof_begin<DT>(x, e0, e1, st);
+    if constexpr (BIG) {
+        launch288q<DT, EPI>(x, grid, st);
+    } else if (ln_tail) {
+        if constexpr (EPI == EPI_GATE_RESIDUAL) {
+            PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI_GATE_RESIDUAL_LN);
+            hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI_GATE_RESIDUAL_LN>), grid, dim3(640), 0, st, PRIMX_GEMM_PASS(x));
+            g_ln_fused = true;
+        }
+    } else if (loader) {
+        if constexpr (FOLD_EPI || LOADER_EPI) {
+            PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI);
+            hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI>), grid, dim3(640), 0, st, PRIMX_GEMM_PASS(x));
+        }
+    } else {
+        if constexpr (!FOLD_EPI) {
+            PRIMX_NOTE_KERNEL("gemm144_dma_kernel<%d, %d>", DT, EPI);
+            hipLaunchKernelGGL((gemm144_dma_kernel<DT, EPI>), grid, dim3(512), 0, st, PRIMX_GEMM_PASS(x));
+        }
+    }
+    if (g_gemm_prof_on) gemm_prof_report<DT>(a, EPI, e0, e1, st);
+}
+
 template <int DT, int EPI, int GATHER = 0>
 int launch(const GemmArgs<DT>& a_in, hipStream_t st, const char* name) {
     GemmArgs<DT> a = a_in;
@@ -1919,20 +1918,9 @@ int launch(const GemmArgs<DT>& a_in, hipStream_t st, const char* name) {
                   name, a.M, a.N, a.K);
     const int mt = (a.M + 127) / 128;
     const bool tail = (a.K % BK) != 0;
-    // 256x288 tile: only where same-box A/B showed a win - the dense-output epilogues with enough workgroups to fill
-    // the chip (fc1 at T = 4096: exactly 256; every large-batch GEMM).  The heads epilogue stays on the 128x144 kernel
-    // (qkv would be 192 workgroups = 75 % of the CUs, and the scatter epilogue spilled at this tile's register budget).
-    bool use_big = !g_no_big && a.N % 288 == 0 && ((a.M + 255) / 256) * (a.N / 288) >= g_big_min &&
-                   (EPI == EPI_LINEAR || EPI == EPI_RES || EPI == EPI_GATE_RESIDUAL);
-    // Heads epilogue on the 256x288 tile (LDS-staged scatter, gemm288q only): tiles must cover whole heads of one
-    // segment and one batch entry.  It already pays at 192 workgroups (qkv at T = 4096: 75 % of the CUs, one round
-    // instead of three rounds of 128x144 tiles); PRIMX_GEMM_BIGHEADS_MIN moves the threshold (0 = never).
-    if (EPI == EPI_HEADS && !g_no_big && g_big_heads_min > 0 && a.heads > 0) {
-        const int per = a.heads * a.dh;
-        // (dh >= 32: the epilogue finds the head of a column with at most 8 compare-subtract steps, 288 / dh <= 9 heads per tile)
-        use_big = a.N % 288 == 0 && per % 288 == 0 && 288 % a.dh == 0 && a.dh % 8 == 0 && a.dh >= 32 && a.rows_per_batch % 256 == 0 &&
-                  (a.M / 256) * (a.N / 288) >= g_big_heads_min;
-    }
+    // 256x288 tile: the heads epilogue by its own rule; of the others the dense-output epilogues with a win there (big_dense_ok)
+    const bool use_big = EPI == EPI_HEADS ? big_heads_ok<DT>(a)
+                                          : (EPI == EPI_LINEAR || EPI == EPI_RES || EPI == EPI_GATE_RESIDUAL) && big_dense_ok(a.M, a.N);
     // (the register-staged kernels check every 16-byte chunk against K: one compare per load buys half the instantiations of a
     // compile-time "K has a tail" flag; the LDS-DMA kernels need K % 64 == 0.  The narrow 128 x 32 tile exists for the epilogues
     // that meet N <= 32 - the VAE's convolutions and plain Linear)
@@ -1961,14 +1949,13 @@ int launch_fold(const GemmArgs<DT>& a, hipStream_t st, const char* name) {
     PRIMX_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % BK == 0 && a.N % 144 == 0,
                   "%s: the fold kernels need N %% 144 == 0 and K %% 64 == 0 (M=%d N=%d K=%d)", name, a.M, a.N, a.K);
     const int mt = (a.M + 127) / 128;
+    bool big;   // the 256 x 288 tile where the unfolded GEMM with the same epilogue takes it (launch<>)
     if constexpr (EPI == EPI_GATE_RESIDUAL_FOLD) {
         PRIMX_REQUIRE(a.N / 144 <= 8, "%s: at most 8 column tiles (N <= 1152), the consumers read 8 partial sums per row (N=%d)", name, a.N);
         PRIMX_REQUIRE((((uintptr_t)a.ln_scale | (uintptr_t)a.ln_out | (uintptr_t)a.fold_part | (uintptr_t)a.fold_c) & 7) == 0 &&
                           a.ln_mod_stride % 4 == 0,
                       "%s: the scale vectors, the operand, the partial sums and the (centre, scale) pairs must be 8-byte aligned", name);
-        // the 256 x 288 tile where the unfolded gate-residual GEMM takes it (launch<>: a large batch)
-        if (!g_no_big && a.N % 288 == 0 && ((a.M + 255) / 256) * (a.N / 288) >= g_big_min) launch144_dma<DT, EPI, 1>(a, mt, st);
-        else launch144_dma<DT, EPI>(a, mt, st);
+        big = big_dense_ok(a.M, a.N);
     } else {
         PRIMX_REQUIRE(a.K % 144 == 0 && a.fold_parts == a.K / 144 && a.fold_parts <= 8,
                       "%s: K must be the producer's N: a multiple of 144, at most 1152 (K=%d)", name, a.K);
@@ -1976,24 +1963,16 @@ int launch_fold(const GemmArgs<DT>& a, hipStream_t st, const char* name) {
                           (((uintptr_t)a.fold_part | (uintptr_t)a.fold_c | (uintptr_t)a.fold_c_out) & 7) == 0,
                       "%s: u / v must be 16-byte aligned, the partial sums and the (centre, scale) pairs 8-byte aligned", name);
         if constexpr (EPI == EPI_HEADS_FOLD) {
-            const int per = a.heads * a.dh;
-            const bool big = !g_no_big && g_big_heads_min > 0 && a.N % 288 == 0 && per % 288 == 0 && 288 % a.dh == 0 && a.dh % 8 == 0 &&
-                             a.dh >= 32 && a.rows_per_batch % 256 == 0 && (a.M / 256) * (a.N / 288) >= g_big_heads_min;
-            if (big) {
-                launch144_dma<DT, EPI, 1>(a, mt, st);
-            } else {
-                bool ok = per % 144 == 0 && a.dh >= 48 && a.dh % 4 == 0 && a.rows_per_batch >= 128 && g_loader;
-                for (int sgi = 0; sgi < a.n_seg; ++sgi) ok = ok && a.kind[sgi] != PRIMX_HEADS_VT;
-                PRIMX_REQUIRE(ok, "%s: head layout outside the fold kernels (heads=%d dh=%d rows_per_batch=%d)", name, a.heads, a.dh,
-                              a.rows_per_batch);
-                launch144_dma<DT, EPI>(a, mt, st);
-            }
+            big = big_heads_ok<DT>(a);
+            if (!big)
+                PRIMX_REQUIRE(loader_heads_ok<DT>(a) && g_loader, "%s: head layout outside the fold kernels (heads=%d dh=%d rows_per_batch=%d)",
+                              name, a.heads, a.dh, a.rows_per_batch);
         } else {
-            const int wgs = ((a.M + 255) / 256) * (a.N / 288);
-            if (!g_no_big && a.N % 288 == 0 && wgs >= g_big_min) launch144_dma<DT, EPI, 1>(a, mt, st);
-            else launch144_dma<DT, EPI>(a, mt, st);
+            big = big_dense_ok(a.M, a.N);
         }
     }
+    if (big) launch144_dma<DT, EPI, 1>(a, mt, st);
+    else launch144_dma<DT, EPI>(a, mt, st);
     PRIMX_CHECK_LAUNCH(name);
     return PRIMX_OK;
 }
@@ -2069,11 +2048,6 @@ __global__ __launch_bounds__(256) void gemv16_kernel(const typename T16<DT>::S* 
     }
 }
 
-static const bool g_no_gemv = [] {
-    const char* e = getenv("PRIMX_GEMM_NOGEMV");
-    return e && e[0] == '1';
-}();
-
 }  // namespace
 
 extern "C" const char* primx_last_gemm_kernel(void) { return g_last_gemm_kernel; }
@@ -2082,6 +2056,68 @@ extern "C" int primx_ln_sync_timeouts(void) {
     unsigned v = 0;
     (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_ln_sync_timeouts), sizeof(v));   // (synchronises with the device)
     return (int)v;
+}
+
+// ---- The argument blocks of GemmArgs, each filled in one place.
+template <int DT>
+static void set_operands(GemmArgs<DT>& a, const void* A, const void* W, const void* bias, int M, int N, int K) {
+    using S = typename T16<DT>::S;
+    a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
+    a.M = M; a.N = N; a.K = K;
+}
+
+// EPI_HEADS / EPI_HEADS_FOLD.  `rep_batches`: batch entries per repetition of the column groups (primx_linear_heads with n_rep > 1); 0
+// for the fold variants, which do not repeat.
+template <int DT>
+static void set_heads(GemmArgs<DT>& a, int rows_per_batch, int heads, int dh, int n_seg, const int* kind, void* const* dst, int n_pad,
+                      float scale0, int rep_batches) {
+    using S = typename T16<DT>::S;
+    a.rows_per_batch = rows_per_batch; a.heads = heads; a.dh = dh; a.DP = primx_padded_head_dim(dh);
+    a.n_pad = n_pad; a.n_seg = n_seg; a.scale0 = scale0;
+    for (int s = 0; s < 3; ++s) {
+        a.kind[s] = s < n_seg ? kind[s] : 0;
+        // one (batch, head) block holds n_pad * row-stride elements in the token-major layouts, DP * n_pad in VT
+        a.rep_stride[s] = (int64_t)rep_batches * heads * n_pad * (a.kind[s] == PRIMX_HEADS_VT ? a.DP : heads_row_stride(a.kind[s], a.DP));
+        a.dst[s] = s < n_seg ? (S*)dst[s] : nullptr;
+    }
+}
+
+template <int DT>
+static void set_gate(GemmArgs<DT>& a, const void* gate, int64_t gate_stride, float* x, int rows_per_batch) {
+    a.gate = (const typename T16<DT>::S*)gate; a.gate_stride = gate_stride; a.x = x; a.rows_per_batch = rows_per_batch;
+}
+
+// the consumer side of a folded LayerNorm site (behind set_operands: fold_parts = K / 144)
+template <int DT>
+static void set_fold_consumer(GemmArgs<DT>& a, const float* part, const float* u, const float* v, const float* center, float* center_out,
+                              float eps) {
+    a.fold_part = const_cast<float*>(part); a.fold_parts = a.K / 144; a.fold_u = u; a.fold_v = v; a.fold_c = center; a.fold_c_out = center_out;
+    a.fold_eps = eps;
+}
+
+// The argument rules of a heads problem: segment count, shape, every segment's kind and destination - the layouts, before any operand
+// or fold pointer.  `what` prefixes the message ("problem 0: ").  n_rep = 1 for the fold variants.  `check_mk`: M and K are checked
+// with the shape (primx_linear_heads leaves them to launch<>, behind its operand check).
+static int check_heads_args(const char* name, const char* what, bool check_mk, int M, int N, int K, int rows_per_batch, int heads, int dh,
+                            int n_seg, const int* kind, void* const* dst, int n_rep, int n_pad) {
+    PRIMX_REQUIRE(kind && dst && n_seg >= 1 && n_seg <= 3 && n_rep >= 1, "%s: %sn_seg must be 1..3, n_rep >= 1", name, what);
+    PRIMX_REQUIRE(heads > 0 && dh > 0 && N == n_rep * n_seg * heads * dh && (!check_mk || (M > 0 && K > 0)),
+                  "%s: %sN must equal n_rep*n_seg*heads*dh", name, what);
+    PRIMX_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && n_pad >= rows_per_batch && n_pad % 16 == 0,
+                  "%s: %sneed M %% rows_per_batch == 0, n_pad >= rows_per_batch, n_pad %% 16 == 0", name, what);
+    for (int s = 0; s < n_seg; ++s) {
+        PRIMX_REQUIRE(kind[s] == PRIMX_HEADS_ROWS || kind[s] == PRIMX_HEADS_VT || kind[s] == PRIMX_HEADS_KROWS, "%s: %sbad kind", name, what);
+        PRIMX_REQUIRE(dst[s] != nullptr, "%s: %snull destination", name, what);
+    }
+    return PRIMX_OK;
+}
+
+// ... and the pointers of a fold-consumer heads problem, behind its layouts
+static int check_heads_fold_pointers(const char* name, const char* what, const void* A, const void* W, const float* part, const float* u,
+                                     const float* v, const float* center, const float* center_out) {
+    PRIMX_REQUIRE(A && W && part && u && v && center && center_out && center != center_out,
+                  "%s: %snull operand or fold argument, or center_out == center", name, what);
+    return PRIMX_OK;
 }
 
 extern "C" int primx_linear(const void* A, const void* W, const void* bias, void* out, int M, int N, int K, int dtype,
@@ -2110,8 +2146,7 @@ extern "C" int primx_linear(const void* A, const void* W, const void* bias, void
     PRIMX_DISPATCH_16(dtype, "primx_linear", {
         using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
-        a.M = M; a.N = N; a.K = K;
+        set_operands<DT>(a, A, W, bias, M, N, K);
         a.out = (S*)out; a.act = act; a.out_scale = out_scale;
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, "primx_linear")) return rc;
         return launch<DT, EPI_LINEAR>(a, (hipStream_t)stream, "primx_linear");
@@ -2125,8 +2160,7 @@ extern "C" int primx_linear_residual(const void* A, const void* W, const void* b
     PRIMX_DISPATCH_16(dtype, "primx_linear_residual", {
         using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
-        a.M = M; a.N = N; a.K = K;
+        set_operands<DT>(a, A, W, bias, M, N, K);
         a.out = (S*)out; a.res = (const S*)res; a.out_scale = scale;
         return launch<DT, EPI_RES>(a, (hipStream_t)stream, "primx_linear_residual");
     });
@@ -2151,9 +2185,8 @@ extern "C" int primx_linear_gate_residual_ln(const void* A, const void* W, const
     PRIMX_DISPATCH_16(dtype, name, {
         using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
-        a.M = M; a.N = N; a.K = K;
-        a.gate = (const S*)gate; a.gate_stride = gate_stride; a.x = x; a.rows_per_batch = rows_per_batch;
+        set_operands<DT>(a, A, W, bias, M, N, K);
+        set_gate<DT>(a, gate, gate_stride, x, rows_per_batch);
         a.ln_shift = (const S*)ln_shift; a.ln_scale = (const S*)ln_scale; a.ln_mod_stride = ln_mod_stride;
         a.ln_out = (S*)ln_out; a.ln_eps = ln_eps; a.sync = (unsigned*)sync;
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
@@ -2176,29 +2209,11 @@ extern "C" int primx_linear_heads(const void* A, const void* W, const void* bias
                                   int rows_per_batch, int heads, int dh, int n_seg, const int* kind, void* const* dst,
                                   int n_rep, int rep_batches, int n_pad, float scale0, int dtype, const void* prefetch,
                                   int64_t prefetch_bytes, void* stream) {
-    PRIMX_REQUIRE(kind && dst && n_seg >= 1 && n_seg <= 3 && n_rep >= 1, "primx_linear_heads: n_seg must be 1..3, n_rep >= 1");
-    PRIMX_REQUIRE(heads > 0 && dh > 0 && N == n_rep * n_seg * heads * dh,
-                  "primx_linear_heads: N must equal n_rep*n_seg*heads*dh");
-    PRIMX_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && n_pad >= rows_per_batch && n_pad % 16 == 0,
-                  "primx_linear_heads: need M %% rows_per_batch == 0, n_pad >= rows_per_batch, n_pad %% 16 == 0");
-    for (int s = 0; s < n_seg; ++s) {
-        PRIMX_REQUIRE(dst[s] != nullptr, "primx_linear_heads: null destination");
-        PRIMX_REQUIRE(kind[s] == PRIMX_HEADS_ROWS || kind[s] == PRIMX_HEADS_VT || kind[s] == PRIMX_HEADS_KROWS,
-                      "primx_linear_heads: bad kind");
-    }
+    if (int rc = check_heads_args("primx_linear_heads", "", false, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, n_rep, n_pad)) return rc;
     PRIMX_DISPATCH_16(dtype, "primx_linear_heads", {
-        using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
-        a.M = M; a.N = N; a.K = K;
-        a.rows_per_batch = rows_per_batch; a.heads = heads; a.dh = dh; a.DP = primx_padded_head_dim(dh);
-        a.n_pad = n_pad; a.n_seg = n_seg; a.scale0 = scale0;
-        for (int s = 0; s < 3; ++s) {
-            a.kind[s] = s < n_seg ? kind[s] : 0;
-            // one (batch, head) block holds n_pad * row-stride elements in the token-major layouts, DP * n_pad in VT
-            a.rep_stride[s] = (int64_t)rep_batches * heads * n_pad * (a.kind[s] == PRIMX_HEADS_VT ? a.DP : heads_row_stride(a.kind[s], a.DP));
-            a.dst[s] = s < n_seg ? (S*)dst[s] : nullptr;
-        }
+        set_operands<DT>(a, A, W, bias, M, N, K);
+        set_heads<DT>(a, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, scale0, rep_batches);
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, "primx_linear_heads")) return rc;
         return launch<DT, EPI_HEADS>(a, (hipStream_t)stream, "primx_linear_heads");
     });
@@ -2317,16 +2332,13 @@ extern "C" int primx_linear_f32out(const void* A, const void* W, const void* bia
     PRIMX_REQUIRE(A && W && out, "primx_linear_f32out: null pointer");
     PRIMX_REQUIRE(M > 0 && N > 0 && K > 0 && K % 8 == 0, "primx_linear_f32out: need M,N>0 and K %% 8 == 0 (M=%d N=%d K=%d)", M, N, K);
     PRIMX_DISPATCH_16(dtype, "primx_linear_f32out", {
-        using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
-        a.M = M; a.N = N; a.K = K;
+        set_operands<DT>(a, A, W, bias, M, N, K);
         a.x = out; a.rows_per_batch = bias_from_row;
         // the loader-wave 128 x 144 kernel where the shape allows (N % 144 == 0, K % 64 == 0; PRIMX_F32OUT_TILE144=0: never) - the fold's
         // u / v rows are 8 - 32 workgroups of 18 k-tiles, latency-bound on the register-staged generic kernel (~20 us each); same box,
         // the configs[1] step: 8.453 - 8.471 -> 8.446 - 8.452 ms (tools/gpu/r4_uv144.sh)
-        static const bool tile144 = [] { const char* e = getenv("PRIMX_F32OUT_TILE144"); return !(e && e[0] == '0'); }();
-        if (tile144 && g_loader && N % 144 == 0 && K % BK == 0 && (((uintptr_t)out | (uintptr_t)bias) & 15) == 0) {
+        if (g_f32out_tile144 && g_loader && N % 144 == 0 && K % BK == 0 && (((uintptr_t)out | (uintptr_t)bias) & 15) == 0) {
             PRIMX_NOTE_KERNEL("gemm144l_dma_kernel<%d, %d>", DT, EPI_F32OUT);
             hipLaunchKernelGGL((gemm144l_dma_kernel<DT, EPI_F32OUT>), dim3(((M + 127) / 128) * (N / 144)), dim3(640), 0,
                                (hipStream_t)stream, PRIMX_GEMM_PASS(a));
@@ -2350,9 +2362,8 @@ extern "C" int primx_linear_gate_residual_fold(const void* A, const void* W, con
     PRIMX_DISPATCH_16(dtype, name, {
         using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W; a.bias = (const S*)bias;
-        a.M = M; a.N = N; a.K = K;
-        a.gate = (const S*)gate; a.gate_stride = gate_stride; a.x = x; a.rows_per_batch = rows_per_batch;
+        set_operands<DT>(a, A, W, bias, M, N, K);
+        set_gate<DT>(a, gate, gate_stride, x, rows_per_batch);
         a.ln_scale = (const S*)next_scale; a.ln_mod_stride = next_mod_stride; a.ln_out = (S*)a16_out;
         a.fold_c = center; a.fold_part = part_out;
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
@@ -2361,58 +2372,22 @@ extern "C" int primx_linear_gate_residual_fold(const void* A, const void* W, con
     return PRIMX_OK;
 }
 
-// The argument rules of a fold-consumer heads problem (primx_linear_heads_fold, problem 0 of primx_linear_heads_fold_pair): the layouts
-// first - segment count, shape, every segment's kind and destination - then the operand and fold pointers.  `what` prefixes the message.
-static int check_heads_fold_args(const char* name, const char* what, const void* A, const void* W, int M, int N, int K, int rows_per_batch,
-                                 int heads, int dh, int n_seg, const int* kind, void* const* dst, int n_pad, const float* part, const float* u,
-                                 const float* v, const float* center, const float* center_out) {
-    PRIMX_REQUIRE(kind && dst && n_seg >= 1 && n_seg <= 3, "%s: %sn_seg must be 1..3", name, what);
-    PRIMX_REQUIRE(heads > 0 && dh > 0 && N == n_seg * heads * dh && M > 0 && K > 0, "%s: %sN must equal n_seg*heads*dh", name, what);
-    PRIMX_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0 && n_pad >= rows_per_batch && n_pad % 16 == 0,
-                  "%s: %sneed M %% rows_per_batch == 0, n_pad >= rows_per_batch, n_pad %% 16 == 0", name, what);
-    for (int s = 0; s < n_seg; ++s) {
-        PRIMX_REQUIRE(kind[s] == PRIMX_HEADS_ROWS || kind[s] == PRIMX_HEADS_VT || kind[s] == PRIMX_HEADS_KROWS, "%s: %sbad kind", name, what);
-        PRIMX_REQUIRE(dst[s] != nullptr, "%s: %snull destination", name, what);
-    }
-    PRIMX_REQUIRE(A && W && part && u && v && center && center_out && center != center_out,
-                  "%s: %snull operand or fold argument, or center_out == center", name, what);
-    return PRIMX_OK;
-}
-
 extern "C" int primx_linear_heads_fold(const void* A, const void* W, int M, int N, int K, int rows_per_batch, int heads, int dh,
                                        int n_seg, const int* kind, void* const* dst, int n_pad, float scale0, const float* part,
                                        const float* u, const float* v, const float* center, float* center_out, float eps,
                                        int dtype, const void* prefetch, int64_t prefetch_bytes, void* stream) {
     const char* name = "primx_linear_heads_fold";
-    if (int rc = check_heads_fold_args(name, "", A, W, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, part, u, v, center,
-                                       center_out))
-        return rc;
+    if (int rc = check_heads_args(name, "", true, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, 1, n_pad)) return rc;
+    if (int rc = check_heads_fold_pointers(name, "", A, W, part, u, v, center, center_out)) return rc;
     PRIMX_DISPATCH_16(dtype, name, {
-        using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W;
-        a.M = M; a.N = N; a.K = K;
-        a.rows_per_batch = rows_per_batch; a.heads = heads; a.dh = dh; a.DP = primx_padded_head_dim(dh);
-        a.n_pad = n_pad; a.n_seg = n_seg; a.scale0 = scale0;
-        for (int s = 0; s < 3; ++s) {
-            a.kind[s] = s < n_seg ? kind[s] : 0;
-            a.rep_stride[s] = 0;
-            a.dst[s] = s < n_seg ? (S*)dst[s] : nullptr;
-        }
-        a.fold_part = const_cast<float*>(part); a.fold_parts = K / 144; a.fold_u = u; a.fold_v = v; a.fold_c = center; a.fold_c_out = center_out; a.fold_eps = eps;
+        set_operands<DT>(a, A, W, nullptr, M, N, K);
+        set_heads<DT>(a, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, scale0, 0);
+        set_fold_consumer<DT>(a, part, u, v, center, center_out, eps);
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
         return launch_fold<DT, EPI_HEADS_FOLD>(a, (hipStream_t)stream, name);
     });
     return PRIMX_OK;
-}
-
-// Does a heads problem map onto the 256 x 288 tile's LDS-staged scatter epilogue (the shape rule of launch<> / launch_fold, without their
-// workgroup-count thresholds)?
-template <int DT>
-static bool big_heads_shape(const GemmArgs<DT>& a) {
-    const int per = a.heads * a.dh;
-    return !g_no_big && g_big_heads_min > 0 && a.heads > 0 && a.N % 288 == 0 && per % 288 == 0 && 288 % a.dh == 0 && a.dh % 8 == 0 &&
-           a.dh >= 32 && a.rows_per_batch % 256 == 0 && a.M % 256 == 0 && a.K % BK == 0;
 }
 
 // primx_linear_heads_fold (problem 0, no carried prefetch) and primx_linear_heads (problem 1: n_rep = 1, no carried prefetch) from ONE
@@ -2426,54 +2401,36 @@ extern "C" int primx_linear_heads_fold_pair(const void* A, const void* W, int M,
                                             int rows_per_batch2, int heads2, int dh2, int n_seg2, const int* kind2, void* const* dst2,
                                             int n_pad2, float scale0_2, int dtype, void* stream) {
     const char* name = "primx_linear_heads_fold_pair";
-    PRIMX_REQUIRE(A2 && W2 && kind2 && dst2 && n_seg2 >= 1 && n_seg2 <= 3, "%s: problem 1: null operand, or n_seg outside 1..3", name);
-    PRIMX_REQUIRE(heads2 > 0 && dh2 > 0 && N2 == n_seg2 * heads2 * dh2 && M2 > 0 && K2 > 0, "%s: problem 1: N must equal n_seg*heads*dh", name);
-    PRIMX_REQUIRE(rows_per_batch2 > 0 && M2 % rows_per_batch2 == 0 && n_pad2 >= rows_per_batch2 && n_pad2 % 16 == 0,
-                  "%s: problem 1: need M %% rows_per_batch == 0, n_pad >= rows_per_batch, n_pad %% 16 == 0", name);
-    for (int s = 0; s < n_seg2; ++s)
-        PRIMX_REQUIRE(dst2[s] != nullptr && (kind2[s] == PRIMX_HEADS_ROWS || kind2[s] == PRIMX_HEADS_VT || kind2[s] == PRIMX_HEADS_KROWS),
-                      "%s: problem 1: null destination or bad kind", name);
+    PRIMX_REQUIRE(A2 && W2, "%s: problem 1: null operand", name);
+    if (int rc = check_heads_args(name, "problem 1: ", true, M2, N2, K2, rows_per_batch2, heads2, dh2, n_seg2, kind2, dst2, 1, n_pad2)) return rc;
     bool paired = false;
     if (A) {
-        if (int rc = check_heads_fold_args(name, "problem 0: ", A, W, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, part, u, v,
-                                           center, center_out))
-            return rc;
+        if (int rc = check_heads_args(name, "problem 0: ", true, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, 1, n_pad)) return rc;
+        if (int rc = check_heads_fold_pointers(name, "problem 0: ", A, W, part, u, v, center, center_out)) return rc;
     }
     PRIMX_DISPATCH_16(dtype, name, {
-        using S = typename T16<DT>::S;
+        // the pair kernel's tiles are whole: on top of the shape rule of launch<> / launch_fold (which get M % 256 == 0 from
+        // rows_per_batch % 256 == 0 and check K themselves) it asks for M % 256 == 0 and K % 64 == 0 explicitly; the workgroup
+        // threshold applies to problem 0 only (below)
+        auto pair_shape = [](const GemmArgs<DT>& p) { return big_heads_shape<DT>(p) && p.M % 256 == 0 && p.K % BK == 0; };
         GemmArgs<DT> r = {};
-        r.A = (const S*)A2; r.W = (const S*)W2; r.bias = (const S*)bias2;
-        r.M = M2; r.N = N2; r.K = K2;
-        r.rows_per_batch = rows_per_batch2; r.heads = heads2; r.dh = dh2; r.DP = primx_padded_head_dim(dh2);
-        r.n_pad = n_pad2; r.n_seg = n_seg2; r.scale0 = scale0_2;
-        for (int s = 0; s < 3; ++s) {
-            r.kind[s] = s < n_seg2 ? kind2[s] : 0;
-            r.rep_stride[s] = 0;
-            r.dst[s] = s < n_seg2 ? (S*)dst2[s] : nullptr;
-        }
-        const bool big1 = big_heads_shape<DT>(r);
-        const int g1 = big1 ? (r.M / 256) * (r.N / 288) : 0;
+        set_operands<DT>(r, A2, W2, bias2, M2, N2, K2);
+        set_heads<DT>(r, rows_per_batch2, heads2, dh2, n_seg2, kind2, dst2, n_pad2, scale0_2, 0);
+        const bool big1 = pair_shape(r);
+        const int g1 = big1 ? big_heads_wgs<DT>(r) : 0;
         if (big1) r.xcd_gm = big_xcd_gm<DT>(r, true);
         if (A) {
             GemmArgs<DT> a = {};
-            a.A = (const S*)A; a.W = (const S*)W;
-            a.M = M; a.N = N; a.K = K;
-            a.rows_per_batch = rows_per_batch; a.heads = heads; a.dh = dh; a.DP = primx_padded_head_dim(dh);
-            a.n_pad = n_pad; a.n_seg = n_seg; a.scale0 = scale0;
-            for (int s = 0; s < 3; ++s) {
-                a.kind[s] = s < n_seg ? kind[s] : 0;
-                a.rep_stride[s] = 0;
-                a.dst[s] = s < n_seg ? (S*)dst[s] : nullptr;
-            }
-            a.fold_part = const_cast<float*>(part); a.fold_parts = K / 144; a.fold_u = u; a.fold_v = v; a.fold_c = center; a.fold_c_out = center_out;
-            a.fold_eps = eps;
-            const int g0 = big_heads_shape<DT>(a) ? (a.M / 256) * (a.N / 288) : 0;
+            set_operands<DT>(a, A, W, nullptr, M, N, K);
+            set_heads<DT>(a, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, scale0, 0);
+            set_fold_consumer<DT>(a, part, u, v, center, center_out, eps);
+            const int g0 = pair_shape(a) ? big_heads_wgs<DT>(a) : 0;
             // one round: both problems' tiles at once on the 256 CUs; problem 0 at the size launch_fold gives the big tile; the fold rules
             if (big1 && g0 >= g_big_heads_min && g0 % 8 == 0 && g0 + g1 <= 256 && !g_gemm_prof_on && K % 144 == 0 && a.fold_parts <= 8 &&
                 (((uintptr_t)u | (uintptr_t)v) & 15) == 0 && (((uintptr_t)part | (uintptr_t)center | (uintptr_t)center_out) & 7) == 0) {
                 a.xcd_gm = big_xcd_gm<DT>(a, true);
                 a.ln_light = g_ln_mode;
-                if (heads_kt64<DT>(a) && heads_kt64<DT>(r)) {
+                if (kt64_ring<DT>(a, EPI_HEADS_FOLD, g0) && kt64_ring<DT>(r, EPI_HEADS, g1)) {
                     PRIMX_NOTE_KERNEL("gemm288q_pair_kernel<%d, 64>", DT);
                     hipLaunchKernelGGL((gemm288q_pair_kernel<DT, 64>), dim3(g0 + g1), dim3(512), 0, (hipStream_t)stream, PRIMX_GEMM_PASS(a), g0, r);
                 } else {
@@ -2507,10 +2464,9 @@ extern "C" int primx_linear_fold(const void* A, const void* W, void* out, int M,
     PRIMX_DISPATCH_16(dtype, name, {
         using S = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const S*)A; a.W = (const S*)W;
-        a.M = M; a.N = N; a.K = K;
+        set_operands<DT>(a, A, W, nullptr, M, N, K);
         a.out = (S*)out; a.act = act; a.out_scale = 1.0f;
-        a.fold_part = const_cast<float*>(part); a.fold_parts = K / 144; a.fold_u = u; a.fold_v = v; a.fold_c = center; a.fold_c_out = center_out; a.fold_eps = eps;
+        set_fold_consumer<DT>(a, part, u, v, center, center_out, eps);
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
         return launch_fold<DT, EPI_LINEAR_FOLD>(a, (hipStream_t)stream, name);
     });
@@ -2526,8 +2482,7 @@ extern "C" int primx_conv3d_k3(const void* in, const void* Wk, const void* bias,
     PRIMX_DISPATCH_16(dtype, "primx_conv3d_k3", {
         using Sx = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const Sx*)in; a.W = (const Sx*)Wk; a.bias = (const Sx*)bias;
-        a.M = P * S * S * S; a.N = Cout; a.K = Kpad;
+        set_operands<DT>(a, in, Wk, bias, P * S * S * S, Cout, Kpad);
         a.out = (Sx*)out; a.res = (const Sx*)res; a.out_scale = res_scale;
         a.S3 = S; a.cin_log2 = cl;
         return launch<DT, EPI_RES, 1>(a, (hipStream_t)stream, "primx_conv3d_k3");
@@ -2542,8 +2497,7 @@ extern "C" int primx_convtranspose_k2s2(const void* in, const void* Wt, const vo
     PRIMX_DISPATCH_16(dtype, "primx_convtranspose_k2s2", {
         using Sx = typename T16<DT>::S;
         GemmArgs<DT> a = {};
-        a.A = (const Sx*)in; a.W = (const Sx*)Wt; a.bias = (const Sx*)bias;
-        a.M = P * S * S * S; a.N = 8 * Cout; a.K = Cin;
+        set_operands<DT>(a, in, Wt, bias, P * S * S * S, 8 * Cout, Cin);
         a.out = (Sx*)out; a.S3 = S; a.cout = Cout;
         return launch<DT, EPI_CONVT>(a, (hipStream_t)stream, "primx_convtranspose_k2s2");
     });

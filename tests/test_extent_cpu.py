@@ -123,7 +123,7 @@ def test_probe_primitives_by_hand():
 
 
 def test_gemm_ring_guard_shapes_as_literals():
-    """The guard of csrc/gemm.hip launch288q / heads_kt64 is M K < 2^31 and N K < 2^31, at K = 1152."""
+    """The guard of csrc/gemm.hip kt64_ring is M K < 2^31 and N K < 2^31, at K = 1152."""
     K = 1152
     assert 1863936 * K == 2147254272 < ex.E <= 2147549184 == 1864192 * K
     assert 1863936 == 7281 * 256 and 1864192 == 7282 * 256                         # M side: whole 256-row tiles

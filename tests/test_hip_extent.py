@@ -574,7 +574,7 @@ def test_gemm_ring_guard_n_side(ops, dtype, N):
 @pytest.mark.parametrize("B", [910, 911])
 def test_gemm_ring_guard_heads(ops, dtype, B):
     """primx_linear_heads, one HEADS_ROWS destination of 16 heads x 72, 2048 rows per batch entry: M = 910 x 2048 (M K =
-    2 146 959 360, the heads_kt64 ring) and M = 911 x 2048 (2 149 318 656: the fallback).  The same row blocks against
+    2 146 959 360, the heads ring of kt64_ring) and M = 911 x 2048 (2 149 318 656: the fallback).  The same row blocks against
     float64 (segment 0: scaled after its rounding), every batch entry against a torch fp32 matmul."""
     from topia_xl_amd._lib import HEADS_ROWS
     n, H, dh, K = 2048, 16, 72, GK
