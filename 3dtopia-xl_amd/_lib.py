@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("PRIMX_LIB") or os.path.join(_HERE, "csrc", "libprimx_
 F32, F16, BF16 = 0, 1, 2
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF = 0, 1, 2
 HEADS_ROWS, HEADS_VT, HEADS_KROWS = 0, 1, 2
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 _p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
@@ -139,6 +139,7 @@ SIGNATURES = {
     "primx_fps": [_p, _i, _i, _i, _p, _l, _p, _p, _p],
     "primx_primsdf_query_backward": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "primx_adam_step": [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p],
+    "primx_raymarch_backward": [_p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # an alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI: version 21 changed the
@@ -157,7 +158,8 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # but VAE.encode / VAE.forward and pipeline.primitives_to_latents); version 32 added the editing entry points (_EDIT_ENTRY_POINTS:
 # a version-31 build serves everything but q_sample, ddim_reverse_sample and the kept-token DDIM loops); version 33 added the
 # primitive-fitting entry points (_FIT_ENTRY_POINTS: a version-32 build serves everything but fit.py); version 34 added the
-# refinement entry points (_REFINE_ENTRY_POINTS: a version-33 build serves everything but the differentiable PrimSDF and refine=)
+# refinement entry points (_REFINE_ENTRY_POINTS: a version-33 build serves everything but the differentiable PrimSDF and refine=);
+# version 35 added primx_raymarch_backward (_RAYMARCH_GRAD_ENTRY_POINTS: a version-34 build serves everything but the marcher's backward)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
@@ -173,7 +175,8 @@ _VAEENC_ENTRY_POINTS: set = {"primx_latent_norm", "primx_enc_conv_in", "primx_co
 _EDIT_ENTRY_POINTS: set = {"primx_q_sample", "primx_diffusion_reverse_step", "primx_diffusion_step_keep"}
 _FIT_ENTRY_POINTS: set = {"primx_mesh_field_query", "primx_mesh_face_areas", "primx_mesh_surface_points", "primx_fps"}
 _REFINE_ENTRY_POINTS: set = {"primx_primsdf_query_backward", "primx_adam_step"}
-_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33)
+_RAYMARCH_GRAD_ENTRY_POINTS: set = {"primx_raymarch_backward"}
+_AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34)
 _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
@@ -242,6 +245,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
         if got < 33 and name in _FIT_ENTRY_POINTS:
             continue
         if got < 34 and name in _REFINE_ENTRY_POINTS:
+            continue
+        if got < 35 and name in _RAYMARCH_GRAD_ENTRY_POINTS:
             continue
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes

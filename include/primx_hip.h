@@ -83,7 +83,7 @@
 extern "C" {
 #endif
 
-#define PRIMX_ABI_VERSION 34
+#define PRIMX_ABI_VERSION 35
 
 /* dtype codes */
 #define PRIMX_F32 0
@@ -880,6 +880,44 @@ int primx_compute_raydirs(const float* viewpos, const float* viewrot, const floa
 int primx_raymarch(const float* raypos, const float* raydir, const float* tminmax, float stepsize, const float* primpos,
                    const float* primrot, const float* primscale, const float* tplate, float* rayrgba, int N, int H, int W,
                    int K, int TD, int TH, int TW, float fadescale, float fadeexp, void* stream);
+
+/* Backward of primx_raymarch (mvpraymarch.py:162-213; raymarch_subset_backward_kernel, mvpraymarch_subset_kernel.h:103-217,
+ * with PrimAccumAdditive::forwardbackward_prim, PrimSamplerTW::backward and PrimTransfSRT::backward).  ABI 35.  The forward's
+ * inputs plus grad_rayrgba [N,H,W,4], the gradient of a scalar loss with respect to rayrgba.  The kernel ADDS, in fp32, into
+ * gtemplate [N,K,TD,TH,TW,4], gprimpos [N,K,3], gprimrot [N,K,3,3] and gprimscale [N,K,3]; the caller zeroes them.  Each may be
+ * null: a null array is neither computed nor touched (all four null: PRIMX_EINVAL).  No forward output is taken: the march is
+ * repeated.  raypos, raydir and tminmax get no gradient, as in the reference.
+ *   - decisions: WHICH samples are taken is decided by the forward's own code (one march skeleton, instantiated by both
+ *     kernels): the per-tile hit list (8 x 8 pixels, index order, 512 cap), the ray's own [rtmin, rtmax], the `incs` start with
+ *     t and rp accumulated separately, the strict |y| < 1 test, t < rtmax + 1e-5 and saturation at newalpha >= 1.  They are
+ *     constants of the differentiation.
+ *   - two sweeps per ray: sweep 1 is the forward accumulation in registers and yields whether the ray saturates and the
+ *     colour S of its saturating sample; sweep 2 computes the gradients.  A ray whose grad_rayrgba is all zero does nothing;
+ *     a wave of such rays returns before the hit list.  An out-of-image lane shadows an edge ray for the hit list, as in the
+ *     forward, and adds nothing (not even zeros).
+ *   - per taken sample of sweep 2, with dL = grad_rayrgba of the ray, raw = the trilinear sample, fade = exp(-fs sum |y_d|^fe),
+ *     a = raw.w fade, A = the running alpha before the sample, sat_now = (A + a dt >= 1), weight = sat_now ? 1 - A : a dt:
+ *       g_rgb = weight dL.rgb;
+ *       g_a   = sat_now ? 0 : dt ((raw.rgb - S) . dL.rgb + (the ray saturates ? 0 : dL.a)), S = 0 on a ray that never saturates;
+ *       nothing is taken after a ray's saturating sample;
+ *       template: corner c of the sample's cell receives w_c (g_rgb, g_a fade);
+ *       local position: g_y = a g_a (-fs fe |y|^(fe-1) sign(y)) + (T-1)/2 sum_c dw_c/dy (raw_c . (g_rgb, g_a fade)), T per axis,
+ *       sign(0) = 0;
+ *       SRT, with xm = x - pos, u_i = sum_j rot[j][i] xm_j, y_i = u_i s_i:  gscale_i += u_i g_y_i;
+ *       grot[j][i] += xm_j s_i g_y_i;  gpos_j -= sum_i rot[j][i] s_i g_y_i.
+ *   - arithmetic: fp32 throughout with the forward's fast exp2 / log2 forms.  Every add is a global fp32 atomic add.  The 15 SRT
+ *     components of one (step, primitive) are first summed over the wave's lanes in a fixed (butterfly) order, then one lane
+ *     adds them; template adds come from the lanes directly, run-length merged: a lane sums consecutive samples of one
+ *     (primitive, cell) in registers and adds the 8 x 4 partial sums when either changes and at the end of its ray.
+ *     The sums depend on the arrival order of the atomics, so the
+ *     results are NOT bitwise reproducible from run to run in general (an address that only one lane adds to, in program
+ *     order, is).
+ * Needs TD, TH, TW > 1, stepsize > 0, and TD * TH * TW and 9 * K below 2^31 (the template gradient is indexed in 64 bits).
+ * Nothing outside the four gradient arrays is written; no workspace, no host synchronisation. */
+int primx_raymarch_backward(const float* raypos, const float* raydir, const float* tminmax, float stepsize,
+                            const float* primpos, const float* primrot, const float* primscale, const float* tplate,
+                            const float* grad_rayrgba, float* gtemplate, float* gprimpos, float* gprimrot, float* gprimscale,
+                            int N, int H, int W, int K, int TD, int TH, int TW, float fadescale, float fadeexp, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * The reference's fp32 call path: DiT.forward(x, t, y) with the signature defaults precision_dtype=float32,
