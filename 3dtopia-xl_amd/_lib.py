@@ -140,6 +140,7 @@ SIGNATURES = {
     "primx_primsdf_query_backward": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "primx_adam_step": [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p],
     "primx_raymarch_backward": [_p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p],
+    "primx_material_sample": [_p, _p, _p, _l, _p, _i, _p, _p, _i, _p, _i, _p, _l, _p, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # an alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI: version 21 changed the
@@ -159,7 +160,9 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # a version-31 build serves everything but q_sample, ddim_reverse_sample and the kept-token DDIM loops); version 33 added the
 # primitive-fitting entry points (_FIT_ENTRY_POINTS: a version-32 build serves everything but fit.py); version 34 added the
 # refinement entry points (_REFINE_ENTRY_POINTS: a version-33 build serves everything but the differentiable PrimSDF and refine=);
-# version 35 added primx_raymarch_backward (_RAYMARCH_GRAD_ENTRY_POINTS: a version-34 build serves everything but the marcher's backward)
+# version 35 added primx_raymarch_backward (_RAYMARCH_GRAD_ENTRY_POINTS: a version-34 build serves everything but the marcher's backward);
+# primx_material_sample (_MATERIAL_ENTRY_POINTS) was added to version 35 without a new number, because it changes no existing call: an
+# A/B build of version 35 from before it lacks the symbol and serves everything but a MeshField with a material
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
@@ -176,6 +179,7 @@ _EDIT_ENTRY_POINTS: set = {"primx_q_sample", "primx_diffusion_reverse_step", "pr
 _FIT_ENTRY_POINTS: set = {"primx_mesh_field_query", "primx_mesh_face_areas", "primx_mesh_surface_points", "primx_fps"}
 _REFINE_ENTRY_POINTS: set = {"primx_primsdf_query_backward", "primx_adam_step"}
 _RAYMARCH_GRAD_ENTRY_POINTS: set = {"primx_raymarch_backward"}
+_MATERIAL_ENTRY_POINTS: set = {"primx_material_sample"}
 _AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34)
 _fold_available: dict = {}
 _blocks_call: dict = {}
@@ -248,6 +252,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
             continue
         if got < 35 and name in _RAYMARCH_GRAD_ENTRY_POINTS:
             continue
+        if ab and name in _MATERIAL_ENTRY_POINTS and not hasattr(lib, name):
+            continue                # an A/B build from before the entry point existed (same version number)
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)

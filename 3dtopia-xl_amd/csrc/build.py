@@ -20,7 +20,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["rowops.hip", "gemm.hip", "attention.hip", "vae.hip", "primsdf.hip", "raymarch.hip", "fp32.hip", "conv3.hip", "conv3s8.hip", "conv3s8c32.hip", "convt.hip", "dit_host.hip", "mcubes.hip", "texbake.hip", "meshclean.hip", "meshdecim.hip", "vaeenc.hip", "meshfield.hip"]
+SOURCES = ["rowops.hip", "gemm.hip", "attention.hip", "vae.hip", "primsdf.hip", "raymarch.hip", "fp32.hip", "conv3.hip", "conv3s8.hip", "conv3s8c32.hip", "convt.hip", "dit_host.hip", "mcubes.hip", "texbake.hip", "meshclean.hip", "meshdecim.hip", "vaeenc.hip", "meshfield.hip", "material.hip"]
 HEADERS = ["common.h", "ln_row.h", "gemm288q_body.inc", "mc_tables.h", "block_scan.h", os.path.join("..", "..", "include", "primx_hip.h")]
 LIB = os.path.join(HERE, "libprimx_hip.so")
 MANIFEST = os.path.join(HERE, "build_manifest.json")
@@ -76,6 +76,8 @@ def check_fresh() -> bool:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     want, have = source_hashes(), _manifest()
+    if not force and os.path.exists(LIB) and have.get("lib") == want["lib"]:
+        return LIB                      # the library matches the sources: nothing to do, even where only it was shipped (no objects)
     objs, jobs, names = [], [], []
     for src in SOURCES:
         name = src.replace(".hip", ".o")

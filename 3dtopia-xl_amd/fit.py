@@ -11,7 +11,8 @@ the reference tree: the defaults below are this project's choice, measured on th
 
 Kernels (csrc/meshfield.hip, rules in include/primx_hip.h "Primitive fitting"): `primx_mesh_field_query` (brute force over
 the faces: exact point-triangle distance, generalized winding number, attributes at the closest point),
-`primx_mesh_face_areas`, `primx_mesh_surface_points`, `primx_fps`.  Torch does the plumbing: the float64 inclusive sum of the
+`primx_mesh_face_areas`, `primx_mesh_surface_points`, `primx_fps`; csrc/material.hip ("Textured meshes"): `primx_material_sample`
+(the glTF material of a `mesh.MaterialMesh` at the closest point).  Torch does the plumbing: the float64 inclusive sum of the
 areas (on the host, where it is sequential and therefore reproducible to the bit), the seeded uniforms (a CPU generator, as the
 sampler draws its noise), the normalisation and the assembly of `recon_param`.
 """
@@ -68,15 +69,64 @@ def mesh_field_query(x: torch.Tensor, v: torch.Tensor, f: torch.Tensor, attr: Op
     return dist, face, wn, out
 
 
+@ops.on_input_device
+def material_sample(uv: torch.Tensor, vattr: Optional[torch.Tensor], face: torch.Tensor, face_material: torch.Tensor,
+                    mat_factor: torch.Tensor, mat_tex: torch.Tensor, tex_desc: torch.Tensor, texels: torch.Tensor) -> torch.Tensor:
+    """uv [n, 2], vattr [n, 6] = (color rgba, rm) or None (all ones), face [n] int32, face_material [F] int32, mat_factor [M, 6],
+    mat_tex [M, 2] int32, tex_desc [T, 4] int64, texels [n_texels, 4] uint8 -> [n, 5] float32 (r, g, b, roughness, metallic), not
+    clipped: primx_material_sample (the rules: include/primx_hip.h "Textured meshes").  Indices outside their tables raise."""
+    _need_cuda("material_sample", uv, vattr, face, face_material, mat_factor, mat_tex, tex_desc, texels)
+    uv, face = uv.float().contiguous(), face.int().contiguous()
+    n, dev = uv.shape[0], uv.device
+    if uv.dim() != 2 or uv.shape[1] != 2 or face.shape != (n,):
+        raise ValueError(f"uv must be [n, 2] and face [n], got {tuple(uv.shape)} and {tuple(face.shape)}")
+    if vattr is not None:
+        vattr = vattr.float().contiguous()
+        if tuple(vattr.shape) != (n, 6):
+            raise ValueError(f"vattr must be [n, 6] (color r, g, b, a, rm x, y), got {tuple(vattr.shape)}")
+    face_material, mat_tex = face_material.int().contiguous(), mat_tex.int().contiguous()
+    mat_factor, tex_desc, texels = mat_factor.float().contiguous(), tex_desc.long().contiguous(), texels.contiguous()
+    F, M, T = face_material.shape[0], mat_factor.shape[0], tex_desc.shape[0]
+    if face_material.dim() != 1 or tuple(mat_factor.shape) != (M, 6) or tuple(mat_tex.shape) != (M, 2) or \
+            tuple(tex_desc.shape) != (T, 4) or texels.dtype != torch.uint8 or texels.dim() != 2 or texels.shape[1] != 4:
+        raise ValueError("face_material must be [F], mat_factor [M, 6], mat_tex [M, 2], tex_desc [T, 4] and texels uint8 [n, 4]")
+    out = torch.empty(n, N_ATTR, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().primx_material_sample(
+        ops._dev(uv, "uv", torch.float32) if n else None, ops._dev(vattr, "vattr", torch.float32) if vattr is not None and n else None,
+        ops._dev(face, "face", torch.int32) if n else None, n, ops._dev(face_material, "face_material", torch.int32), F,
+        ops._dev(mat_factor, "mat_factor", torch.float32), ops._dev(mat_tex, "mat_tex", torch.int32), M,
+        ops._dev(tex_desc, "tex_desc", torch.int64) if T else None, T, texels.data_ptr() if texels.shape[0] else None,
+        texels.shape[0], status.data_ptr(), out.data_ptr() if n else None, ops._stream()), "primx_material_sample")
+    return out
+
+
 class MeshField:
     """The signed distance, colour and material functions of a triangle mesh: `query(x)` -> {'sdf' [n, 1], 'tex' [n, 3],
     'mat' [n, 2], 'face' [n], 'wn' [n]}.  sdf = the distance to the closest triangle outside and its negative inside, where
     inside means |winding number| >= 0.5 (negative inside, as PrimSDF stores it); tex / mat are the vertex attributes at the
-    closest point, clipped to [0, 1] (zeros without attributes)."""
+    closest point, clipped to [0, 1] (zeros without attributes).
 
-    def __init__(self, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None):
+    With `material` (a `mesh.MaterialMesh`; its v and f are not used, `v` and `f` are) tex / mat are the mesh's glTF material at
+    the closest point instead: the field query interpolates [vt | color | rm] (C = 8) and `primx_material_sample` evaluates
+    factors and textures there.  The tables and the texel blob are uploaded once, here."""
+
+    def __init__(self, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None):
         _need_cuda("mesh_field", v, f, attr)
         self.v, self.f = _mesh_args(v, f)
+        self.material = None
+        if material is not None:
+            if attr is not None:
+                raise ValueError("give attr or material, not both")
+            dev = self.v.device
+            attr = material.vertex_attr().to(dev)
+            if attr.shape[0] != self.v.shape[0] or material.face_material.shape[0] != self.f.shape[0]:
+                raise ValueError("the material needs one row of vt / color / rm per vertex and one face_material per face")
+            desc, texels = material.texture_tables()
+            self.material = tuple(t.to(dev).contiguous() for t in (material.face_material.int(), material.mat_factor.float(),
+                                                                   material.mat_tex.int(), desc, texels))
+            self.attr = attr.float().contiguous()
+            return
         if attr is not None and tuple(attr.shape) != (self.v.shape[0], N_ATTR):
             raise ValueError(f"attr must be [V, {N_ATTR}] (r, g, b, roughness, metallic), got {tuple(attr.shape)}")
         self.attr = None if attr is None else attr.float().contiguous()
@@ -84,6 +134,8 @@ class MeshField:
     def query(self, x: torch.Tensor) -> dict:
         dist, face, wn, a = mesh_field_query(x, self.v, self.f, self.attr)
         sdf = torch.where(wn.abs() >= 0.5, -dist, dist)[:, None]
+        if self.material is not None:
+            a = material_sample(a[:, 0:2], a[:, 2:8], face, *self.material)
         if a is None:
             a = torch.zeros(x.shape[0], N_ATTR, dtype=torch.float32, device=dist.device)
         a = a.clip(0, 1)
@@ -92,8 +144,8 @@ class MeshField:
     __call__ = query
 
 
-def mesh_field(v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None) -> MeshField:
-    return MeshField(v, f, attr)
+def mesh_field(v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None) -> MeshField:
+    return MeshField(v, f, attr, material)
 
 
 @ops.on_input_device
@@ -176,14 +228,17 @@ def _local_grid(S: int, dev) -> torch.Tensor:
 
 
 def _mesh_parts(mesh, dev):
+    """-> (v, f, attr [V, 5] or None, material or None): a `mesh.MaterialMesh` keeps its material, everything else today's attr."""
+    t = lambda a: torch.as_tensor(a).to(dev)   # noqa: E731
+    if hasattr(mesh, "face_material"):
+        return t(mesh.v).float(), t(mesh.f).int(), None, mesh
     if isinstance(mesh, (tuple, list)):
         v, f, albedo, rough, metal = mesh
     else:
         v, f, albedo, rough, metal = mesh.v, mesh.f, mesh.albedo, mesh.roughness, mesh.metallic
-    t = lambda a: torch.as_tensor(a).to(dev)   # noqa: E731
     v, f = t(v).float(), t(f).int()
     attr = torch.cat([t(albedo).float().reshape(-1, 3), t(rough).float().reshape(-1, 1), t(metal).float().reshape(-1, 1)], 1)
-    return v, f, attr.contiguous()
+    return v, f, attr.contiguous(), None
 
 
 REFINE_SCALE_FLOOR = 1e-4  # the scale is clamped to this after every step (fitted scales are positive; 0 would cover nothing)
@@ -254,7 +309,8 @@ def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, 
 def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candidates: Optional[int] = None, seed: int = 0,
                        normalize: bool = True, extent: float = 0.9, device=None, chunk: int = 1 << 20, refine: int = 0,
                        refine_kw: Optional[dict] = None):
-    """mesh: a `mesh.TriMesh` or (v, f, albedo [V, 3], roughness [V], metallic [V]) -> (recon_param [P, 4 + 6 S^3], info).
+    """mesh: a `mesh.TriMesh`, (v, f, albedo [V, 3], roughness [V], metallic [V]) or a `mesh.MaterialMesh` (e.g. from
+    `mesh.read_glb`: colour and material come from its textures and factors) -> (recon_param [P, 4 + 6 S^3], info).
 
     `candidates` (default 32 P) surface samples drawn with `seed`; P of them by farthest point sampling from candidate 0;
     scale = distance to the nearest other centre; payload in `PrimSDF.feat_param`'s layout [sdf | rgb | roughness, metallic],
@@ -272,7 +328,7 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
     if not 1 <= P <= N:
         raise ValueError(f"num_prims must lie in 1 .. candidates (got {P} of {N})")
     with torch.cuda.device(dev), torch.no_grad():
-        v, f, attr = _mesh_parts(mesh, dev)
+        v, f, attr, material = _mesh_parts(mesh, dev)
         v, f = _mesh_args(v, f)
         center, scale = torch.tensor([0.0, 0.0, 0.0], device=dev), torch.tensor(1.0, device=dev)
         if normalize:
@@ -282,7 +338,7 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
         idx, nn = fps(cand, P, 0)
         pos = cand[idx.long()]
         x = (pos[:, None, :] + nn[:, None, None] * _local_grid(S, dev)[None]).reshape(-1, 3)
-        field = MeshField(v, f, attr)
+        field = MeshField(v, f, attr, material)
         parts = [field.query(x[lo:lo + chunk]) for lo in range(0, x.shape[0], chunk)]
         sdf = torch.cat([q["sdf"] for q in parts]).reshape(P, S ** 3)
         a = torch.cat([torch.cat([q["tex"], q["mat"]], 1) for q in parts]).reshape(P, S ** 3, N_ATTR)
@@ -290,7 +346,7 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
         rinfo = None
         if int(refine) > 0:
             recon, rinfo = refine_primitives(recon, field, int(refine), **{"chunk": chunk, **(refine_kw or {})})
-    info = {"center": center, "scale": scale, "v": v, "f": f, "attr": attr, "candidates": cand, "candidate_face": cface, "idx": idx}
+    info = {"center": center, "scale": scale, "v": v, "f": f, "attr": field.attr if material is not None else attr, "candidates": cand, "candidate_face": cface, "idx": idx}
     if rinfo is not None:
         info["refine"] = rinfo
     return recon, info

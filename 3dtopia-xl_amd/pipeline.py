@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from .fit import mesh_field, mesh_to_primitives, refine_primitives  # noqa: F401  (fitting a user's mesh: fit.py)
-from .mesh import read_ply                               # noqa: F401
+from .mesh import read_glb, read_ply                     # noqa: F401
 
 
 _STATS_CACHE: dict = {}

@@ -4,14 +4,18 @@
         scale = nearest-centre distance, payload = the mesh's signed distance / colour / material per voxel)
         -> PrimSDF -> extract_mesh -> PLY            [-> primitives_to_latents with --vae: the 68-channel tokens]
 
-Without --ply a coloured torus is written first and read back, so the run is end to end on a written PLY.  The fit is the
+--mesh takes a .ply or a .glb (glTF 2.0 binary: UVs, textures, material factors, several materials, node transforms - what
+`mesh.read_glb` documents); a GLB is fitted from its textures (`primx_material_sample` at the closest surface point of every
+voxel) and comes back as a textured GLB: `extract_texmesh` -> `TexturedMesh.write_glb`.  Without --mesh a coloured torus is
+written first and read back, so the run is end to end on a written PLY, and the loop is then closed on a GLB as well: the fitted
+torus is extracted as a textured GLB, that file is read back with `read_glb` and fitted again.  The fit is the
 initialisation the 3DTopia-XL paper describes; --refine N follows it with N steps of gradient refinement against the mesh's own
 field and reports the field error at the surface candidates before and after.  Without --vae the encoder carries
 random weights (the tokens are then noise: the point is the data flow and the per-stage timing).  (The file is not called
 tokenize.py: a script directory is searched for modules first, and that name would replace the standard library's `tokenize`
 for every script in examples/.)
 
-    python examples/tokenize_mesh.py [--ply IN.ply] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--vae VAE.pt] [--denoised OUT.pt]
+    python examples/tokenize_mesh.py [--mesh IN.ply | IN.glb] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--vae VAE.pt] [--denoised OUT.pt]
 """
 import argparse
 import math
@@ -42,7 +46,9 @@ def torus(nu=192, nv=96, R=0.6, r=0.25):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ply", default=None, help="input mesh (binary PLY as TriMesh.write_ply writes it); a torus when absent")
+    ap.add_argument("--mesh", "--ply", dest="ply", default=None,
+                    help="input mesh: a binary PLY as TriMesh.write_ply writes it, or a glTF 2.0 .glb; a torus when absent")
+    ap.add_argument("--texture-size", type=int, default=1024, help="texture size of the GLBs written")
     ap.add_argument("--out", default="tokenized.ply", help="the mesh extracted from the fitted primitives")
     ap.add_argument("--denoised", default=None, help="also save the primitives as a denoised.pt")
     ap.add_argument("--prims", type=int, default=2048)
@@ -73,7 +79,13 @@ def main():
         path = os.path.splitext(a.out)[0] + "_input.ply"
         M.TriMesh(*torus()).write_ply(path)
         print("wrote the input torus ->", path)
-    mesh = timed("read_ply", lambda: pipeline.read_ply(path, device=dev))
+    is_glb = path.lower().endswith(".glb")
+    if is_glb:
+        mesh = timed("read_glb", lambda: pipeline.read_glb(path, device=dev))
+        print(f"  {mesh.mat_factor.shape[0]} materials, {mesh.tex_image.shape[0]} textures, images "
+              + ", ".join(f"{i.shape[1]}x{i.shape[0]}" for i in mesh.images))
+    else:
+        mesh = timed("read_ply", lambda: pipeline.read_ply(path, device=dev))
     print(f"  V = {mesh.v.shape[0]}  F = {mesh.f.shape[0]}")
     timed("mesh_to_primitives (first call)", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed))
     recon, info = timed("mesh_to_primitives", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed))
@@ -96,16 +108,38 @@ def main():
     report(field, "fitted")
     if a.refine > 0:
         from topia_xl_amd import fit
-        target = fit.MeshField(info["v"], info["f"], info["attr"])
+        target = fit.MeshField(info["v"], info["f"], material=mesh) if is_glb else fit.MeshField(info["v"], info["f"], info["attr"])
         fit.refine_primitives(recon, target, 1)                                       # (first call: loads the kernels)
         recon, rinfo = timed(f"refine_primitives, {a.refine} steps", lambda: fit.refine_primitives(recon, target, a.refine))
         print(f"  loss {rinfo['loss'][0]:.3e} -> {rinfo['loss'][-1]:.3e}")
         field = as_field(recon)
         report(field, "refined")
-    out = timed(f"extract_mesh {a.resolution}^3", lambda: M.extract_mesh(field, resolution=a.resolution))
-    print(f"  V = {out.v.shape[0]}  F = {out.f.shape[0]}")
-    out.write_ply(a.out)
-    print("extracted mesh ->", a.out)
+    glb_out = os.path.splitext(a.out)[0] + ".glb"
+    if is_glb:
+        tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size))
+        print(f"  V = {tex.v.shape[0]}  F = {tex.f.shape[0]}")
+        tex.write_glb(glb_out)
+        print("extracted textured mesh ->", glb_out)
+    else:
+        out = timed(f"extract_mesh {a.resolution}^3", lambda: M.extract_mesh(field, resolution=a.resolution))
+        print(f"  V = {out.v.shape[0]}  F = {out.f.shape[0]}")
+        out.write_ply(a.out)
+        print("extracted mesh ->", a.out)
+    if a.ply is None:
+        # close the loop on this project's own textured GLB: tokens -> GLB -> read_glb -> tokens
+        tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size))
+        tex.write_glb(glb_out)
+        back = timed("read_glb (the GLB just written)", lambda: pipeline.read_glb(glb_out, device=dev))
+        print(f"  V = {back.v.shape[0]}  F = {back.f.shape[0]}  images " + ", ".join(f"{i.shape[1]}x{i.shape[0]}" for i in back.images))
+        recon2, info2 = timed("mesh_to_primitives (textured GLB)",
+                              lambda: pipeline.mesh_to_primitives(back, num_prims=a.prims, seed=a.seed))
+        info = info2
+        report(as_field(recon2), "refitted from the GLB:")
+        with torch.no_grad():
+            q = field(info2["candidates"] / info2["scale"] + info2["center"])
+            c2 = as_field(recon2)(info2["candidates"])
+        d = (torch.cat([c2["tex"], c2["mat"]], 1) - torch.cat([q["tex"], q["mat"]], 1)).abs()
+        print(f"  colour / material of the refit against the first fit at its surface candidates: mean {float(d.mean()):.3e}  max {float(d.max()):.3e}")
     if not a.no_encode:
         vae = pkg.VAE(in_channels=6, latent_channels=1, out_channels=6, down_channels=[32, 256], mid_attention=True,
                       up_channels=[256, 32], layers_per_block=2)

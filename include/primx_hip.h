@@ -992,6 +992,40 @@ int primx_mesh_surface_points(const float* v, const int* f, int V, int F, const 
  * One launch per centre, no host synchronisation; ws: 4 N (rounded up to 8) + 4096 bytes, 8-byte aligned, any contents. */
 int primx_fps(const float* pts, int N, int K, int start, void* ws, int64_t ws_bytes, int* idx, float* nn, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Textured meshes (csrc/material.hip; added to ABI 35 without a new version number: the call is purely additive): the glTF 2.0 metallic-roughness material of a mesh at the closest surface
+ * point of every query point.  The closest-point search is primx_mesh_field_query's: called with attr = [vt | color | rm]
+ * (C = 8) it returns per point the interpolated UV, the vertex colour (r, g, b, a), the vertex multipliers of roughness and
+ * metallic, and the face.  tests/material_numpy.py restates the rules below in float64 / float32.  Every expression is
+ * evaluated as written, uncontracted; the output equals the float32 restatement bit for bit.
+ *
+ * uv [n, 2], vattr [n, 6] = (color.r, color.g, color.b, color.a, rm.x, rm.y) or NULL (all ones), face [n] in [0, F),
+ * face_material [F] in [0, M), mat_factor [M, 6] = (baseColorFactor r, g, b, a, roughnessFactor, metallicFactor),
+ * mat_tex [M, 2] = (base-colour texture, metallic-roughness texture), each in [-1, T), -1 = none, tex_desc [T, 4] int64 =
+ * (offset of the texture's first texel in the blob, counted in texels, W, H, flags), flags = wrapS | wrapT << 2 |
+ * nearest << 4 with wrap 0 = CLAMP_TO_EDGE, 1 = REPEAT, 2 = MIRRORED_REPEAT, W and H in 1 .. 65536, texels [n_texels, 4]
+ * uint8 RGBA (row-major, row 0 first; 4-byte aligned) -> out [n, 5] = (r, g, b, roughness, metallic), not clipped.
+ *   - texel (i, j) of a W x H texture has its centre at u = (i + 0.5) / W, v = (j + 0.5) / H; image row 0 is v = 0.
+ *   - a non-finite u or v samples as 0.  LINEAR: x = u * W - 0.5, clamped to [-2^30, 2^30] (so the conversion to int is
+ *     defined for every u; beyond 2^24 x is an integer anyway), i0 = floor(x), fx = x - i0, i1 = i0 + 1; the same for y from v, H.
+ *     NEAREST: i = floor(u * W), the floor clamped to [-2^30, 2^30], j likewise.
+ *   - wrap per axis, on the integers: CLAMP_TO_EDGE min(max(i, 0), W - 1); REPEAT i mod W (non-negative); MIRRORED_REPEAT
+ *     t = i mod 2 W (non-negative), then t < W ? t : 2 W - 1 - t.
+ *   - channel = float(byte) / 255.0f (correctly rounded), bytes as stored: no sRGB decode.
+ *   - LINEAR texel = (t00 (1 - fx) + t10 fx) (1 - fy) + (t01 (1 - fx) + t11 fx) fy, t10 = the texel at (i1, j0); a material
+ *     without a texture samples 1.0.
+ *   - r, g, b = (factor.rgb * color.rgb) * base.rgb; roughness = (roughnessFactor * rm.x) * mr.g; metallic =
+ *     (metallicFactor * rm.y) * mr.b.  Alpha (factor.a, color.a, the textures') is not used.
+ * No output is NaN while vattr and mat_factor are finite.  One thread per point (64-bit point index), no atomics on the output:
+ * deterministic.  A face outside [0, F), a material outside [0, M), a texture index outside [-1, T) and a descriptor that is
+ * malformed or runs past the blob return PRIMX_EINVAL; nothing is read out of bounds (every thread checks each link of
+ * face -> material -> texture -> descriptor before it follows it; a second launch checks the whole tables) and the points
+ * concerned get 0.  status: one int of scratch.  The call synchronises the stream once, where it reads the check back.
+ * -------------------------------------------------------------------------------------------- */
+int primx_material_sample(const float* uv, const float* vattr, const int* face, int64_t n, const int* face_material, int F,
+                          const float* mat_factor, const int* mat_tex, int M, const int64_t* tex_desc, int T,
+                          const uint8_t* texels, int64_t n_texels, int* status, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
