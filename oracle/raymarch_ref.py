@@ -38,9 +38,12 @@ def compute_raydirs(viewpos, viewrot, focal, princpt, pixelcoords, volradius):
     d = torch.einsum("nhwi,nij->nhwj", d, viewrot)                  # row0 * d.x + row1 * d.y + row2 * d.z
     d = d / d.norm(dim=-1, keepdim=True)
     t1, t2 = (-1.0 - raypos) / d, (1.0 - raypos) / d
-    tmin = torch.minimum(t1, t2).amax(-1)
-    tmax = torch.maximum(t1, t2).amin(-1)
-    return raypos.contiguous(), d, torch.stack([tmin.clamp(min=0.0), tmax], dim=-1)
+    # fminf / fmaxf as in utils_kernel.cu:45-49: a lone NaN (0 / 0: an origin coordinate of exactly +-1 with a direction component of
+    # exactly 0, a ray lying in a face plane of the volume) is DROPPED, where torch.minimum / maximum / amax would propagate it
+    lo, hi = torch.fmin(t1, t2), torch.fmax(t1, t2)
+    tmin = torch.fmax(lo[..., 0], torch.fmax(lo[..., 1], lo[..., 2]))
+    tmax = torch.fmin(hi[..., 0], torch.fmin(hi[..., 1], hi[..., 2]))
+    return raypos.contiguous(), d, torch.stack([torch.fmax(tmin, torch.zeros_like(tmin)), tmax], dim=-1)
 
 
 def raymarch(raypos, raydir, tminmax, stepsize, primpos, primrot, primscale, template_chlast, fadescale, fadeexp):

@@ -104,8 +104,10 @@ def test_raydirs_and_march_against_oracle():
     rp, rd, tmm = raymarch_ref.compute_raydirs(campos, camrot, focal, princpt, pc, volradius)
     grp, grd, gtm = rm.compute_raydirs(campos.to(DEV), camrot.to(DEV), focal.to(DEV), princpt.to(DEV), pc.to(DEV), volradius)
     assert (grp.cpu() - rp).abs().max() < 1e-6 and (grd.cpu() - rd).abs().max() < 1e-5
-    fin = torch.isfinite(tmm) & torch.isfinite(gtm.cpu())
-    assert (gtm.cpu()[fin] - tmm[fin]).abs().max() < 1e-4
+    # a generic camera: every t is finite on both sides, so ALL of the t-range is compared (tests/test_hip_raydirs.py holds the
+    # cameras whose rays have exact zeros and infinities, element by element)
+    assert bool(torch.isfinite(tmm).all()) and bool(torch.isfinite(gtm).all())
+    assert (gtm.cpu() - tmm).abs().max() < 1e-4
     # image: march the oracle on the DEVICE's rays (so that step alignment is compared, not ray rounding)
     ref = raymarch_ref.raymarch(grp.cpu(), grd.cpu(), gtm.cpu(), dt / volradius, pos / volradius, rot, scale,
                                 rgba.permute(0, 1, 3, 4, 5, 2).contiguous(), 8.0, 8.0)
