@@ -40,13 +40,15 @@ class DitForwardFold(C.Structure):
                                   "b_from", "step", "n_steps")] + \
                [("ln_eps", _f), ("scale", _f)] + \
                [(n, _p) for n in ("h", "xn", "att", "hid", "Qc", "Qs", "Ks", "Vs", "mod", "center0", "center1", "part")] + \
-               [(n, _p) for n in ("kv_A", "kv_W", "kv_bias")] + [(n, _i) for n in ("kv_rows", "kv_rows_per_batch", "kv_K")]   # ABI 25
+               [(n, _p) for n in ("kv_A", "kv_W", "kv_bias")] + [(n, _i) for n in ("kv_rows", "kv_rows_per_batch", "kv_K")] + \
+               [("null_vrow", _p)] + [(n, _i) for n in ("only_block", "only_launch", "side")]   # ABI 25; the null cross-attention skip's tail
 
 
 # name -> argument ctypes (return type is always int unless listed in _RESTYPES)
 SIGNATURES = {
     "primx_dit_blocks_fold": [C.POINTER(DitForwardFold), C.POINTER(DitBlockFold), _p],
     "primx_abi_version": [],
+    "primx_dit_blocks_fold_features": [],
     "primx_last_error": [],
     "primx_last_gemm_kernel": [],
     "primx_padded_head_dim": [_i],
@@ -185,6 +187,7 @@ _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
 _f32out_group: dict = {}
+_null_skip: dict = {}
 
 _lib: Optional[C.CDLL] = None
 
@@ -252,7 +255,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
             continue
         if got < 35 and name in _RAYMARCH_GRAD_ENTRY_POINTS:
             continue
-        if ab and name in _MATERIAL_ENTRY_POINTS and not hasattr(lib, name):
+        if ab and (name in _MATERIAL_ENTRY_POINTS or name == "primx_dit_blocks_fold_features") and not hasattr(lib, name):
             continue                # an A/B build from before the entry point existed (same version number)
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
@@ -261,6 +264,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     _blocks_call[path] = got >= 24
     _kv_ride[path] = got >= 25
     _f32out_group[path] = got >= 26
+    _null_skip[path] = got >= 35 and hasattr(lib, "primx_dit_blocks_fold_features") and bool(lib.primx_dit_blocks_fold_features() & 1)
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -288,6 +292,13 @@ def f32out_group_available() -> bool:
     """Does the loaded library carry primx_linear_f32out_group (ABI 26)?"""
     load()
     return _f32out_group.get(LIB_PATH, False)
+
+
+def null_skip_available() -> bool:
+    """Does the loaded library's primx_dit_blocks_fold read the null cross-attention skip's tail of PrimxDitForwardFold?  (False only
+    for a PRIMX_LIB A/B build from before it; same version number, told apart by primx_dit_blocks_fold_features.)"""
+    load()
+    return _null_skip.get(LIB_PATH, False)
 
 
 def check(status: int, name: str) -> None:

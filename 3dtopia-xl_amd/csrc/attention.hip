@@ -334,10 +334,15 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) sc[kt][r] -= delta;   // the tile at hand was formed against the old max
+                // (`first`: O is still zero and stays so.  Not multiplied: a first tile whose row max lies below -128 in the exp2
+                // domain has alpha = 2^(-max) = inf in fp32, and 0 x inf put NaN into every output of that row - finite scores,
+                // tests/test_hip_null_identity.py.  From the second tile on delta >= 0 and alpha <= 1.)
+                if (!first) {
 #pragma unroll
-                for (int t = 0; t < DTILES; ++t)
+                    for (int t = 0; t < DTILES; ++t)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+                        for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+                }
             }
         } else if (!__all((mx - m_run) * c <= RESCALE_THR)) {
             const float m_new = fmaxf(m_run, mx);

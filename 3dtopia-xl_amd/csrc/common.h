@@ -9,6 +9,19 @@
 // ------------------------------------------------------------------ error plumbing
 void primx_set_error(const char* fmt, ...);
 
+// ------------------------------------------------------------------ library-internal GEMM calls (csrc/gemm.hip; issued by csrc/dit_host.hip)
+// primx_linear_gate_residual_fold / primx_linear_heads_fold with the arguments of the null cross-attention skip: `a_row` - the one
+// row every row of A from `a_row_from` on is read from; `mirror` - the row offset of the rows whose statistics the launch finishes
+// without multiplying them.  `name`: the entry point the error messages speak for.
+int primx_gate_residual_fold_rows(const void* A, const void* W, const void* bias, const void* gate, int64_t gate_stride, float* x, int M, int N,
+                                  int K, int rows_per_batch, const void* next_scale, int64_t next_mod_stride, const float* center,
+                                  void* a16_out, float* part_out, const void* a_row, int a_row_from, int dtype, const void* prefetch,
+                                  int64_t prefetch_bytes, void* stream, const char* name);
+int primx_heads_fold_rows(const void* A, const void* W, int M, int N, int K, int rows_per_batch, int heads, int dh, int n_seg, const int* kind,
+                          void* const* dst, int n_pad, float scale0, const float* part, const float* u, const float* v, const float* center,
+                          float* center_out, float eps, int mirror, int dtype, const void* prefetch, int64_t prefetch_bytes, void* stream,
+                          const char* name);
+
 #define PRIMX_REQUIRE(cond, ...)          \
     do {                                  \
         if (!(cond)) {                    \

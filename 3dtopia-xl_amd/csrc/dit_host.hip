@@ -13,6 +13,8 @@
         return PRIMX_EINVAL;          \
     } while (0)
 
+extern "C" int primx_dit_blocks_fold_features(void) { return 1; }
+
 extern "C" int primx_dit_blocks_fold(const PrimxDitForwardFold* f, const PrimxDitBlockFold* blocks, void* stream) {
     if (!f || !blocks) PRIMX_FAIL("primx_dit_blocks_fold: null descriptor");
     if (f->dtype != PRIMX_F16 && f->dtype != PRIMX_BF16) PRIMX_FAIL("primx_dit_blocks_fold: dtype must be PRIMX_F16 or PRIMX_BF16");
@@ -41,6 +43,30 @@ extern "C" int primx_dit_blocks_fold(const PrimxDitForwardFold* f, const PrimxDi
         rc = (x);                  \
         if (rc != PRIMX_OK) return rc; \
     } while (0)
+    // The null cross-attention skip (primx_hip.h, PrimxDitForwardFold::null_vrow): Tc = the rows of the entries that attend
+    const bool skip = f->null_vrow != nullptr;
+    const int Tc = f->b_from * N;
+    if (skip && !(f->b_from > 0 && Be == 2 * f->b_from))
+        PRIMX_FAIL("primx_dit_blocks_fold: null_vrow needs 0 < b_from and Be == 2 b_from (b_from %d, Be %d)", f->b_from, Be);
+    auto vrow = [&](int i) -> const void* { return skip ? static_cast<const char*>(f->null_vrow) + (int64_t)i * D * 2 : nullptr; };
+    // to_q of a block behind the first: the fold consumer over all rows - or over the attending entries' rows, finishing the other rows' statistics
+    auto to_q_fold = [&](const PrimxDitBlockFold& b, int sd) -> int {
+        const float *u, *v;
+        uv(b.uv_q, D, u, v);
+        return primx_heads_fold_rows(f->xn, b.w_q, skip ? Tc : T, D, D, N, H, dh, 1, kq, dq, f->nq_pad, f->scale, f->part, u, v, center[sd],
+                                     center[sd ^ 1], f->ln_eps, skip ? Tc : 0, dt, b.carry_q, b.carry_q_bytes, stream, "primx_linear_heads_fold");
+    };
+    auto cproj = [&](const PrimxDitBlockFold& b, int i, int sd) -> int {
+        return primx_gate_residual_fold_rows(f->att, b.w_cproj, b.b_cproj, ch(i, 2), 0, f->h, T, D, D, N, ch(i, 4), 0, center[sd], f->xn, f->part,
+                                             vrow(i), Tc, dt, b.carry_cproj, b.carry_cproj_bytes, stream, "primx_linear_gate_residual_fold");
+    };
+    if (f->only_launch) {
+        const int i = f->only_block;
+        if (!skip || i < 0 || i >= f->depth || (f->side != 0 && f->side != 1) || (f->only_launch != 1 && f->only_launch != 2) ||
+            (f->only_launch == 1 && (i == 0 || !blocks[i].uv_q || !blocks[i].w_q)) || (f->only_launch == 2 && !blocks[i].w_cproj))
+            PRIMX_FAIL("primx_dit_blocks_fold: bad single launch (launch %d of block %d, side %d)", f->only_launch, i, f->side);
+        return f->only_launch == 1 ? to_q_fold(blocks[i], f->side) : cproj(blocks[i], i, f->side);
+    }
     // ABI 25: the to_k / to_v projection of the conditioning tokens (attention.py:106-107) issued from here - block 0's as a launch of its
     // own, block i + 1's on the CUs block i's qkv launch leaves idle (primx_linear_heads_fold_pair)
     const int kkv[2] = {PRIMX_HEADS_KROWS, PRIMX_HEADS_VT};
@@ -72,15 +98,16 @@ extern "C" int primx_dit_blocks_fold(const PrimxDitForwardFold* f, const PrimxDi
             side = 0;
         }
         if (b.uv_q) {
-            uv(b.uv_q, D, u, v);
-            PRIMX_DIT_CALL(primx_linear_heads_fold(f->xn, b.w_q, T, D, D, N, H, dh, 1, kq, dq, f->nq_pad, f->scale, f->part, u, v, center[side],
-                                                   center[side ^ 1], f->ln_eps, dt, b.carry_q, b.carry_q_bytes, stream));
+            PRIMX_DIT_CALL(to_q_fold(b, side));
             side ^= 1;
         } else {
-            PRIMX_DIT_CALL(primx_linear_heads(f->xn, b.w_q, b.b_q, T, D, D, N, H, dh, 1, kq, dq, 1, 0, f->nq_pad, f->scale, dt, b.carry_q,
+            PRIMX_DIT_CALL(primx_linear_heads(f->xn, b.w_q, b.b_q, skip ? Tc : T, D, D, N, H, dh, 1, kq, dq, 1, 0, f->nq_pad, f->scale, dt, b.carry_q,
                                               b.carry_q_bytes, stream));
         }
-        if (f->b_from < Be) {
+        if (skip) {
+            if (!b.Kc || !b.Vc) PRIMX_FAIL("primx_dit_blocks_fold: block %d: null cross-attention operand", i);
+            PRIMX_DIT_CALL(primx_attention(f->Qc, b.Kc, b.Vc, f->att, f->b_from, H, N, f->nq_pad, f->L, f->nkv_pad_c, dh, f->scale, dt, stream));
+        } else if (f->b_from < Be) {
             if (!b.Kb || !b.Vb || (f->b_from > 0 && (!b.Kc || !b.Vc))) PRIMX_FAIL("primx_dit_blocks_fold: block %d: null cross-attention operand", i);
             PRIMX_DIT_CALL(primx_attention_bcast(f->Qc, f->b_from > 0 ? b.Kc : nullptr, f->b_from > 0 ? b.Vc : nullptr, f->att, Be, H, N, f->nq_pad,
                                                  f->L, f->b_from > 0 ? f->nkv_pad_c : f->nkv_pad_b, dh, f->scale, b.Kb, b.Vb, f->b_from,
@@ -89,8 +116,7 @@ extern "C" int primx_dit_blocks_fold(const PrimxDitForwardFold* f, const PrimxDi
             if (!b.Kc || !b.Vc) PRIMX_FAIL("primx_dit_blocks_fold: block %d: null cross-attention operand", i);
             PRIMX_DIT_CALL(primx_attention(f->Qc, b.Kc, b.Vc, f->att, Be, H, N, f->nq_pad, f->L, f->nkv_pad_c, dh, f->scale, dt, stream));
         }
-        PRIMX_DIT_CALL(primx_linear_gate_residual_fold(f->att, b.w_cproj, b.b_cproj, ch(i, 2), 0, f->h, T, D, D, N, ch(i, 4), 0, center[side], f->xn,
-                                                       f->part, dt, b.carry_cproj, b.carry_cproj_bytes, stream));
+        PRIMX_DIT_CALL(cproj(b, i, side));
         // ---- self-attention over the primitive tokens (dit_crossattn.py:56, attention.py:48-59)
         uv(b.uv_qkv, 3 * D, u, v);
         if (f->kv_A && i + 1 < f->depth) {

@@ -113,6 +113,14 @@ struct GemmArgs {
     const float* fold_c;
     float* fold_c_out;
     float fold_eps;
+    // Null cross-attention skip (dit.py `null_xattn_skip`).  Producer: the row tiles from row a_bcast_from on read ONE row, a_bcast
+    // [K], as every row of A (row stride 0 in the loader's address; a_bcast_from a multiple of the row tile); rows of A from there on
+    // are never touched.  Consumer: fold_mirror > 0 - the column tile 0 workgroup of rows [m0, m0 + BM) also finishes the statistics
+    // of rows fold_mirror + [m0, m0 + BM), which no tile of this launch multiplies (fold_part / fold_c / fold_c_out span M +
+    // fold_mirror rows): same formula, same bits as the launch over all rows would have written.
+    const S* a_bcast;
+    int a_bcast_from;
+    int fold_mirror;
 };
 
 // Weight prefetch carried by a GEMM launch (the `prefetch` / `prefetch_bytes` arguments of primx_linear, primx_linear_heads,
@@ -171,11 +179,11 @@ __device__ __forceinline__ pf_u32x2 gemm_prefetch_lines_tail(const GemmArgs<DT>&
 // loaded behind the first DMAs.
 #define PRIMX_GEMM_PARAMS(DT)                                                                                                \
     const typename T16<DT>::S *pl_A, const typename T16<DT>::S *pl_W, int pl_M, int pl_N, int pl_K, int pl_xcd_gm, int pl_prof, \
-        const GemmArgs<DT> pl_rest
+        const typename T16<DT>::S *pl_Ab, int pl_ab_from, const GemmArgs<DT> pl_rest
 // (no local copy of the struct with the scalars patched in: the dynamically indexed members - kind[], dst[], rep_stride[] - would
 // turn it into a scratch array; the kernels name the leading arguments directly and read everything else through `p`)
 #define PRIMX_GEMM_ARGS(DT) const GemmArgs<DT>& p = pl_rest
-#define PRIMX_GEMM_PASS(x) (x).A, (x).W, (x).M, (x).N, (x).K, (x).xcd_gm, (x).prof, (x)
+#define PRIMX_GEMM_PASS(x) (x).A, (x).W, (x).M, (x).N, (x).K, (x).xcd_gm, (x).prof, (x).a_bcast, (x).a_bcast_from, (x)
 
 // Activation of the EPI_LINEAR epilogue.  `p.act` is uniform, but both branches are pure arithmetic, so hipcc if-converts
 // them: every element then paid for the tanh form AND the erf polynomial (~40 VALU instructions instead of ~12; the fc1
@@ -1190,7 +1198,8 @@ __global__ __launch_bounds__(640) void gemm144l_dma_kernel(PRIMX_GEMM_PARAMS(DT)
     // fold consumer, behind the ring: (mu', rho) of the tile's 128 rows, then u and v of its 144 columns - fetched ONCE per workgroup
     // at kernel start (every thread loading the vectors of its nine units from L2 was 147 KB through the L1 per workgroup: to_q
     // 19.2 vs 17.7 us)
-    constexpr int STAT_HALVES = FOLD_C ? BM * 4 + 2 * BN * 2 : 0;
+    // (+ BM pairs nobody reads: where the mirrored rows of GemmArgs::fold_mirror leave theirs - they run the SAME instructions as the tile's own rows)
+    constexpr int STAT_HALVES = FOLD_C ? BM * 4 + 2 * BN * 2 + BM * 4 : 0;
     static_assert((LDS_HALVES + STAT_HALVES) * 2 <= 160 * 1024 && NINST % 2 == 0, "LDS budget / loader split");
     __shared__ __attribute__((aligned(16))) S smem[LDS_HALVES + STAT_HALVES];
     // (Round 2 left an untested option here - the LOADER waves fetching 5 of the 9 fp32 residual row-chunks of every thread by
@@ -1215,11 +1224,13 @@ __global__ __launch_bounds__(640) void gemm144l_dma_kernel(PRIMX_GEMM_PARAMS(DT)
         // ---------------- loader wave lw: instructions t = lw * 17 + i, rows 8t .. 8t+7 of the 272-row stage image
         const int lw = wave - 8;
         const S* gp[NL];
+        // (producer, tile-uniform: the row tiles from pl_ab_from on read the one row pl_Ab as every row of A - GemmArgs::a_bcast)
+        const bool a_one = FOLD_P && pl_Ab != nullptr && m0 >= pl_ab_from;
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int row = 8 * (lw * NL + i) + (lane >> 3);
             const int c = (lane & 7) ^ ((row >> 1) & 7);
-            gp[i] = (row < BM) ? pl_A + (int64_t)min(m0 + row, pl_M - 1) * pl_K + c * 8
+            gp[i] = (row < BM) ? (a_one ? pl_Ab + c * 8 : pl_A + (int64_t)min(m0 + row, pl_M - 1) * pl_K + c * 8)
                                : pl_W + (int64_t)(n0 + row - BM) * pl_K + c * 8;
         }
         auto issue = [&](int kt, int stage) {
@@ -1280,8 +1291,22 @@ __global__ __launch_bounds__(640) void gemm144l_dma_kernel(PRIMX_GEMM_PARAMS(DT)
     FoldPartials fpart;
     f32x2 fu2 = {0.f, 0.f}, fv2 = {0.f, 0.f};
     const int tuv = tid - BM;                                                            // threads 128 .. 199: two columns each
+    // GemmArgs::fold_mirror: waves 4, 5 of a column tile 0 workgroup own the mirrored rows (wave-uniform).  ONE call site for both kinds
+    // of rows - the same instructions, hence the same bits, as the launch that multiplies those rows runs on them (two call sites
+    // contracted mean + centre differently: 1 ulp in a few per cent of the rows); the mirrored rows' LDS pairs go behind u / v, unread.
+    const bool st_own = wave < BM / 64;
+    [[maybe_unused]] bool st_rows = false, st_tile0 = false;
+    [[maybe_unused]] int st_m0 = m0, st_M = pl_M, st_t = tid;
+    [[maybe_unused]] f32x2* st_dst = fstat;
     if constexpr (FOLD_C) {
-        if (wave < BM / 64) fpart = fold_stats_load<DT>(p, pl_M, m0, tid);
+        const bool mirror = p.fold_mirror > 0 && n0 == 0 && wave >= 4 && wave < 4 + BM / 64;
+        st_rows = st_own || mirror;
+        st_tile0 = n0 == 0;
+        if (mirror) {
+            st_m0 = m0 + p.fold_mirror; st_M = pl_M + p.fold_mirror; st_t = tid - 256;
+            st_dst = reinterpret_cast<f32x2*>(smem + LDS_HALVES + BM * 4 + 2 * BN * 2);
+        }
+        if (st_rows) fpart = fold_stats_load<DT>(p, st_M, st_m0, st_t);
         else if (tuv < BN / 2) {
             fu2 = *reinterpret_cast<const f32x2*>(p.fold_u + n0 + 2 * tuv);
             fv2 = *reinterpret_cast<const f32x2*>(p.fold_v + n0 + 2 * tuv);
@@ -1289,7 +1314,7 @@ __global__ __launch_bounds__(640) void gemm144l_dma_kernel(PRIMX_GEMM_PARAMS(DT)
     }
     const pf_u32x2 pf_v = gemm_prefetch_lines<DT>(p, wave, lane);                        // (the launch's prefetch range)
     if constexpr (FOLD_C) {
-        if (wave < BM / 64) fold_stats_finish<DT>(p, fpart, pl_M, pl_K, m0, tid, n0 == 0, fstat);
+        if (st_rows) fold_stats_finish<DT>(p, fpart, st_M, pl_K, st_m0, st_t, st_tile0, st_dst);
         else if (tuv < BN / 2) {
             *reinterpret_cast<f32x2*>(fu + 2 * tuv) = fu2;
             *reinterpret_cast<f32x2*>(fu + BN + 2 * tuv) = fv2;
@@ -1575,7 +1600,7 @@ constexpr int gemm288q_lds_halves() {
     constexpr int BM = 256, BN = 288, NST = KT == 64 ? 2 : 4, STAGE = (BM + BN) * KT, RS_ROWS = BN + 16, RS_VT = BM + 16;
     constexpr bool HEADS = EPI == EPI_HEADS || EPI == EPI_HEADS_FOLD, FOLD_C = EPI == EPI_HEADS_FOLD || EPI == EPI_LINEAR_FOLD;
     constexpr int STG = HEADS ? ((BM * RS_ROWS > BN * RS_VT) ? BM * RS_ROWS : BN * RS_VT) : 0;
-    return ((NST * STAGE > STG) ? NST * STAGE : STG) + (FOLD_C ? BM * 4 + 2 * BN * 2 : 0);
+    return ((NST * STAGE > STG) ? NST * STAGE : STG) + (FOLD_C ? BM * 4 + 2 * BN * 2 + BM * 4 : 0);
 }
 // The kernel's body lives in gemm288q_body.inc (textual include: the pair kernel below instantiates it twice in one kernel)
 template <int DT, int EPI, int KT = 32>
@@ -1603,6 +1628,8 @@ __global__ __launch_bounds__(512, 2) void gemm288q_pair_kernel(PRIMX_GEMM_PARAMS
         constexpr int EPI = EPI_HEADS;
         const GemmArgs<DT>& p = r;
         const typename T16<DT>::S *const pl_A = r.A, *const pl_W = r.W;
+        [[maybe_unused]] const typename T16<DT>::S* const pl_Ab = nullptr;
+        [[maybe_unused]] const int pl_ab_from = 0;
         const int pl_M = r.M, pl_N = r.N, pl_K = r.K, pl_xcd_gm = r.xcd_gm, pl_prof = 0, bid = (int)blockIdx.x - n0;
 #include "gemm288q_body.inc"
     }
@@ -1956,7 +1983,13 @@ int launch_fold(const GemmArgs<DT>& a, hipStream_t st, const char* name) {
                           a.ln_mod_stride % 4 == 0,
                       "%s: the scale vectors, the operand, the partial sums and the (centre, scale) pairs must be 8-byte aligned", name);
         big = big_dense_ok(a.M, a.N);
+        if (a.a_bcast)   // the one-row source of the rows from a_bcast_from on: whole row tiles of the kernel that runs
+            PRIMX_REQUIRE(a.a_bcast_from > 0 && a.a_bcast_from < a.M && a.a_bcast_from % (big ? 256 : 128) == 0 && ((uintptr_t)a.a_bcast & 15) == 0,
+                          "%s: the broadcast row must be 16-byte aligned and start at a row tile boundary inside the rows (from row %d, M=%d, %d-row tiles)",
+                          name, a.a_bcast_from, a.M, big ? 256 : 128);
     } else {
+        PRIMX_REQUIRE(a.fold_mirror == 0 || a.fold_mirror >= a.M, "%s: the mirrored statistics rows must lie behind the M rows (offset %d, M=%d)", name,
+                      a.fold_mirror, a.M);
         PRIMX_REQUIRE(a.K % 144 == 0 && a.fold_parts == a.K / 144 && a.fold_parts <= 8,
                       "%s: K must be the producer's N: a multiple of 144, at most 1152 (K=%d)", name, a.K);
         PRIMX_REQUIRE((((uintptr_t)a.fold_u | (uintptr_t)a.fold_v) & 15) == 0 &&
@@ -2352,12 +2385,13 @@ extern "C" int primx_linear_f32out(const void* A, const void* W, const void* bia
     return PRIMX_OK;
 }
 
-extern "C" int primx_linear_gate_residual_fold(const void* A, const void* W, const void* bias, const void* gate,
-                                               int64_t gate_stride, float* x, int M, int N, int K, int rows_per_batch,
-                                               const void* next_scale, int64_t next_mod_stride, const float* center,
-                                               void* a16_out, float* part_out, int dtype, const void* prefetch,
-                                               int64_t prefetch_bytes, void* stream) {
-    const char* name = "primx_linear_gate_residual_fold";
+// The two fold GEMMs of the cross-attention branch with the arguments of the null cross-attention skip (common.h; issued by
+// primx_dit_blocks_fold - csrc/dit_host.hip): the entry points below are these with the skip's arguments zero.
+//   a_row / a_row_from: the rows from a_row_from on read the ONE row a_row [K] as their row of A (GemmArgs::a_bcast)
+int primx_gate_residual_fold_rows(const void* A, const void* W, const void* bias, const void* gate, int64_t gate_stride, float* x, int M, int N,
+                                  int K, int rows_per_batch, const void* next_scale, int64_t next_mod_stride, const float* center,
+                                  void* a16_out, float* part_out, const void* a_row, int a_row_from, int dtype, const void* prefetch,
+                                  int64_t prefetch_bytes, void* stream, const char* name) {
     PRIMX_REQUIRE(gate && x && rows_per_batch > 0 && next_scale && center && a16_out && part_out, "%s: bad argument", name);
     PRIMX_DISPATCH_16(dtype, name, {
         using S = typename T16<DT>::S;
@@ -2366,8 +2400,38 @@ extern "C" int primx_linear_gate_residual_fold(const void* A, const void* W, con
         set_gate<DT>(a, gate, gate_stride, x, rows_per_batch);
         a.ln_scale = (const S*)next_scale; a.ln_mod_stride = next_mod_stride; a.ln_out = (S*)a16_out;
         a.fold_c = center; a.fold_part = part_out;
+        a.a_bcast = (const S*)a_row; a.a_bcast_from = a_row ? a_row_from : 0;
         if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
         return launch_fold<DT, EPI_GATE_RESIDUAL_FOLD>(a, (hipStream_t)stream, name);
+    });
+    return PRIMX_OK;
+}
+
+extern "C" int primx_linear_gate_residual_fold(const void* A, const void* W, const void* bias, const void* gate,
+                                               int64_t gate_stride, float* x, int M, int N, int K, int rows_per_batch,
+                                               const void* next_scale, int64_t next_mod_stride, const float* center,
+                                               void* a16_out, float* part_out, int dtype, const void* prefetch,
+                                               int64_t prefetch_bytes, void* stream) {
+    return primx_gate_residual_fold_rows(A, W, bias, gate, gate_stride, x, M, N, K, rows_per_batch, next_scale, next_mod_stride, center, a16_out,
+                                         part_out, nullptr, 0, dtype, prefetch, prefetch_bytes, stream, "primx_linear_gate_residual_fold");
+}
+
+//   mirror: > 0 - part / center / center_out span M + mirror rows, and the launch also finishes the statistics of rows mirror .. mirror + M - 1,
+//   which it does not multiply (GemmArgs::fold_mirror)
+int primx_heads_fold_rows(const void* A, const void* W, int M, int N, int K, int rows_per_batch, int heads, int dh, int n_seg, const int* kind,
+                          void* const* dst, int n_pad, float scale0, const float* part, const float* u, const float* v, const float* center,
+                          float* center_out, float eps, int mirror, int dtype, const void* prefetch, int64_t prefetch_bytes, void* stream,
+                          const char* name) {
+    if (int rc = check_heads_args(name, "", true, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, 1, n_pad)) return rc;
+    if (int rc = check_heads_fold_pointers(name, "", A, W, part, u, v, center, center_out)) return rc;
+    PRIMX_DISPATCH_16(dtype, name, {
+        GemmArgs<DT> a = {};
+        set_operands<DT>(a, A, W, nullptr, M, N, K);
+        set_heads<DT>(a, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, scale0, 0);
+        set_fold_consumer<DT>(a, part, u, v, center, center_out, eps);
+        a.fold_mirror = mirror;
+        if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
+        return launch_fold<DT, EPI_HEADS_FOLD>(a, (hipStream_t)stream, name);
     });
     return PRIMX_OK;
 }
@@ -2376,18 +2440,8 @@ extern "C" int primx_linear_heads_fold(const void* A, const void* W, int M, int 
                                        int n_seg, const int* kind, void* const* dst, int n_pad, float scale0, const float* part,
                                        const float* u, const float* v, const float* center, float* center_out, float eps,
                                        int dtype, const void* prefetch, int64_t prefetch_bytes, void* stream) {
-    const char* name = "primx_linear_heads_fold";
-    if (int rc = check_heads_args(name, "", true, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, 1, n_pad)) return rc;
-    if (int rc = check_heads_fold_pointers(name, "", A, W, part, u, v, center, center_out)) return rc;
-    PRIMX_DISPATCH_16(dtype, name, {
-        GemmArgs<DT> a = {};
-        set_operands<DT>(a, A, W, nullptr, M, N, K);
-        set_heads<DT>(a, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, scale0, 0);
-        set_fold_consumer<DT>(a, part, u, v, center, center_out, eps);
-        if (int rc = set_prefetch<DT>(a, prefetch, prefetch_bytes, name)) return rc;
-        return launch_fold<DT, EPI_HEADS_FOLD>(a, (hipStream_t)stream, name);
-    });
-    return PRIMX_OK;
+    return primx_heads_fold_rows(A, W, M, N, K, rows_per_batch, heads, dh, n_seg, kind, dst, n_pad, scale0, part, u, v, center, center_out, eps, 0,
+                                 dtype, prefetch, prefetch_bytes, stream, "primx_linear_heads_fold");
 }
 
 // primx_linear_heads_fold (problem 0, no carried prefetch) and primx_linear_heads (problem 1: n_rep = 1, no carried prefetch) from ONE

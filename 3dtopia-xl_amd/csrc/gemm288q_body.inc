@@ -23,7 +23,8 @@
     constexpr bool FOLD_P = EPI == EPI_GATE_RESIDUAL_FOLD;         // producer
     constexpr int STG = HEADS ? ((BM * RS_ROWS > BN * RS_VT) ? BM * RS_ROWS : BN * RS_VT) : 0;
     constexpr int LDS_HALVES = (NST * STAGE > STG) ? NST * STAGE : STG;
-    constexpr int STAT_HALVES = FOLD_C ? BM * 4 + 2 * BN * 2 : 0;  // behind the staging area: (mu', rho) of the tile's rows, u and v of its columns
+    // behind the staging area: (mu', rho) of the tile's rows, u and v of its columns, the unread pairs of the mirrored rows (GemmArgs::fold_mirror)
+    constexpr int STAT_HALVES = FOLD_C ? BM * 4 + 2 * BN * 2 + BM * 4 : 0;
     static_assert((LDS_HALVES + STAT_HALVES) * 2 <= 160 * 1024, "LDS budget");
     // (the LDS block belongs to the __global__ wrapper - gemm288q_lds_halves - so that two bodies can share one kernel: gemm288q_pair_kernel)
 
@@ -48,13 +49,16 @@
     const S* gp[KT == 64 ? 1 : NSLOT];
     unsigned go[KT == 64 ? NSLOT : 1];
     constexpr int NA_SLOTS = BM / RPI / 8;
+    // (producer, tile-uniform: the row tiles from pl_ab_from on read the one row pl_Ab as every row of A - GemmArgs::a_bcast)
+    const bool a_one = FOLD_P && pl_Ab != nullptr && m0 >= pl_ab_from;
+    const S* const a_base = a_one ? pl_Ab : pl_A;
     if constexpr (KT == 64) {
 #pragma unroll
         for (int i = 0; i < NSLOT; ++i) {
             const int t = min(wave + 8 * i, NINST - 1);
             const int row = RPI * t + (lane >> 3);
             const int c = (lane & 7) ^ ((row >> 1) & 7);   // LDS position (row, 16-byte slot lane & 7) holds chunk slot ^ ((row >> 1) & 7) (lds_off)
-            go[i] = (unsigned)(((i < NA_SLOTS ? (int64_t)min(m0 + row, pl_M - 1) : (int64_t)(n0 + row - BM)) * pl_K + c * 8) * 2);
+            go[i] = (unsigned)(((i < NA_SLOTS ? (a_one ? (int64_t)0 : (int64_t)min(m0 + row, pl_M - 1)) : (int64_t)(n0 + row - BM)) * pl_K + c * 8) * 2);
         }
     } else {
 #pragma unroll
@@ -62,7 +66,7 @@
             const int t = min(wave + 8 * i, NINST - 1);
             const int row = 16 * t + (lane >> 2);
             const int c = (lane & 3) ^ (((row >> 3) & 1) << 1);
-            gp[i] = (row < BM) ? pl_A + (int64_t)min(m0 + row, pl_M - 1) * pl_K + c * 8
+            gp[i] = (row < BM) ? (a_one ? pl_Ab + c * 8 : pl_A + (int64_t)min(m0 + row, pl_M - 1) * pl_K + c * 8)
                                : pl_W + (int64_t)(n0 + row - BM) * pl_K + c * 8;
         }
     }
@@ -72,7 +76,7 @@
         // GEMM slower, the step 9.05 -> 10.16 ms; the 16 - 32 workgroups of an XCD that share a weight panel then miss in L2)
         if (i < NSLOT - 1 || last_slot) {
             if constexpr (KT == 64)
-                __builtin_amdgcn_global_load_lds((GV*)(uintptr_t)(reinterpret_cast<const char*>((i < NA_SLOTS ? pl_A : pl_W) + ks * KS) + go[i]),
+                __builtin_amdgcn_global_load_lds((GV*)(uintptr_t)(reinterpret_cast<const char*>((i < NA_SLOTS ? a_base : pl_W) + ks * KS) + go[i]),
                                                  (LV*)(smem + stage * STAGE + (wave + 8 * i) * 512), 16, 0, 0);
             else
                 __builtin_amdgcn_global_load_lds((GV*)(uintptr_t)(gp[i] + ks * KS),
@@ -99,12 +103,25 @@
     FoldPartials fpart;
     f32x2 fu2 = {0.f, 0.f}, fv2 = {0.f, 0.f};
     const int tuv = tid - BM;                                                            // threads 256 .. 399: two columns each
+    // GemmArgs::fold_mirror: waves 4 .. 7 of a column tile 0 workgroup own the mirrored rows, next to the u / v columns of waves 4 .. 6.  ONE call
+    // site for both kinds of rows: the same instructions, hence the same bits (see gemm144l_dma_kernel).
+    const bool st_own = wave < BM / 64;
+    [[maybe_unused]] bool st_rows = false, st_tile0 = false;
+    [[maybe_unused]] int st_m0 = m0, st_M = pl_M, st_t = tid;
+    [[maybe_unused]] f32x2* st_dst = fstat;
     if constexpr (FOLD_C) {
-        if (wave < BM / 64) fpart = fold_stats_load<DT>(p, pl_M, m0, tid);
-        else if (tuv < BN / 2) {
+        const bool mirror = p.fold_mirror > 0 && ni_t == 0 && !st_own;
+        st_rows = st_own || mirror;
+        st_tile0 = ni_t == 0;
+        if (mirror) {
+            st_m0 = m0 + p.fold_mirror; st_M = pl_M + p.fold_mirror; st_t = tuv;
+            st_dst = reinterpret_cast<f32x2*>(smem + LDS_HALVES + BM * 4 + 2 * BN * 2);
+        }
+        if (!st_own && tuv < BN / 2) {
             fu2 = *reinterpret_cast<const f32x2*>(p.fold_u + n0 + 2 * tuv);
             fv2 = *reinterpret_cast<const f32x2*>(p.fold_v + n0 + 2 * tuv);
         }
+        if (st_rows) fpart = fold_stats_load<DT>(p, st_M, st_m0, st_t);
     }
 #pragma unroll
     for (int pre = 0; pre < (KT == 64 ? 2 : NST - 1); ++pre)
@@ -112,11 +129,11 @@
         for (int i = 0; i < NSLOT; ++i)
             if (KT == 32 || pre < nks) issue_one(min(pre, nks - 1), pre, i);
     if constexpr (FOLD_C) {
-        if (wave < BM / 64) fold_stats_finish<DT>(p, fpart, pl_M, pl_K, m0, tid, ni_t == 0, fstat);
-        else if (tuv < BN / 2) {
+        if (!st_own && tuv < BN / 2) {
             *reinterpret_cast<f32x2*>(fu + 2 * tuv) = fu2;
             *reinterpret_cast<f32x2*>(fu + BN + 2 * tuv) = fv2;
         }
+        if (st_rows) fold_stats_finish<DT>(p, fpart, st_M, pl_K, st_m0, st_t, st_tile0, st_dst);
     }
     // Fragment prefetch: the A fragments and the first NPF W fragments of slice ks+1 are read while the MFMAs of slice ks
     // run (they need slice ks+1 to have landed one barrier earlier: "vmcnt(4)" = only slice ks+2 still in flight).

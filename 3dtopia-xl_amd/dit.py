@@ -112,6 +112,7 @@ class DiT(nn.Module):
     """Diffusion transformer over primitive tokens (models/dit_crossattn.py:111-213)."""
 
     LN_EPS = 1e-6
+    NULL_SKIP_HEAD_DIMS = (32, 64, 72)   # head dims at which the walk's result for identical keys is asserted to be the value row (`null_xattn_skip`)
 
     def __init__(self, seq_length=2, in_channels=4, condition_channels=512, hidden_size=1152, depth=28,
                  num_heads=16, mlp_ratio=4.0, cond_drop_prob=0.0, attn_proj_bias=False, learn_sigma=True,
@@ -150,13 +151,20 @@ class DiT(nn.Module):
         # the reference does (bench.py quotes its rates against the FLOPs a step executes and reports the algorithmic count of
         # the reference's step next to them).
         self.reuse_cond_kv = False
-        # Second opt-in exact-algebra shortcut, CFG forwards only: the unconditional half is conditioned on ONE row repeated L
-        # times (`y_null = null_cond_embedding.expand_as(y)`, dit_crossattn.py:207), so its L keys are identical, its softmax
-        # is uniform whatever the query, and its cross-attention output is the (identical) value row of every head - to_q and
-        # the attention core of that half compute nothing else.  With this flag they are skipped and the value row is broadcast;
-        # to_k / to_v, proj and everything else run as before.  Off by default (the headline attends; what it does NOT repeat is
-        # the projection of the L identical null rows - `dedup_null_kv` below, 2 % of the algorithmic FLOPs).  Measured at batch 1 (round 3): NO gain (8.55 vs 8.47 ms per step next to reuse_cond_kv) - the
-        # half-size to_q and attention launches occupy half of the CUs for the same time; it pays from batch 2 per GPU on.
+        # CFG forwards only: the unconditional half is conditioned on ONE row repeated L times (`y_null =
+        # null_cond_embedding.expand_as(y)`, dit_crossattn.py:207), so its L keys are identical, its softmax is uniform whatever the
+        # query, and its cross-attention output is the (identical) value row of every head - to_q and the attention core of that
+        # half compute nothing else.
+        # `null_xattn_skip` (default on, with `dedup_null_kv`; PRIMX_NULL_XATTN_SKIP=0 keeps the walk): to_q and the attention
+        # launch cover the conditional entries only and the cross proj reads the value row as every unconditional row of its A
+        # operand (row stride 0 in the GEMM's loader; unfolded forwards: the row is copied into `att`).  BIT-IDENTICAL to the
+        # walk, because the kernel's own result for such an entry is the value row bit for bit (tests/test_hip_null_identity.py)
+        # - under the condition that the scores are finite, and with a -0 of the value row coming out as +0 as the walk's
+        # accumulation leaves it.  The LayerNorm fold, the one-call route and the K / V riders carry it (include/primx_hip.h,
+        # PrimxDitForwardFold::null_vrow).  Not with `cfg_streams` (each half is a chain of its own there).
+        self.null_xattn_skip = os.environ.get("PRIMX_NULL_XATTN_SKIP", "1") != "0"
+        # `collapse_null_cross_attention`: the opt-in from before the skip (round 3) - the same shortcut without `dedup_null_kv`
+        # and without the -0 rule ("exact algebra up to rounding"); unfolded forwards only, a folded forward ignores it.
         self.collapse_null_cross_attention = False
         # Opt-in: run the two classifier-free-guidance halves of `forward_with_cfg` as two concurrent HIP streams
         # (_forward16); identical kernels and results per row.  PRIMX_CFG_STREAMS=1 turns it on for every model.
@@ -717,6 +725,18 @@ class DiT(nn.Module):
             Vn = self._heads("Vn", self.depth, Ln, HEADS_VT, dt, dev, ops.BKV)
             Kn_blk, Vn_blk = Kn.view(self.depth, 1, *Kn.shape[1:]), Vn.view(self.depth, 1, *Vn.shape[1:])
         need_kv = bool(self.depth) and not (self.reuse_cond_kv and cs["kv_valid"] and cs.get("kv_id") == (Kc.data_ptr(), Vc.data_ptr()))
+        two_streams = bool(self.cfg_streams and null_half and self.depth and ops.PROFILE is None)
+        # `null_xattn_skip`: the unconditional entries' to_q and attention walk are not run (see __init__).  Only at the head dims
+        # whose kernel forms tests/test_hip_null_identity.py holds to the value-row property (72: max carried in Q's spare columns;
+        # 64, 32: whole fragments) - any other head dim walks as before; D % 8: the value rows are read in 16-byte pieces
+        skip = (bool(self.null_xattn_skip) and dedup and not two_streams and dh in self.NULL_SKIP_HEAD_DIMS and D % 8 == 0
+                and _lib.null_skip_available())
+
+        def null_value_rows() -> torch.Tensor:
+            # [depth, D] 16-bit: per block the value row of the H heads side by side, out of the broadcast entry's V^T layout [1, H, DP,
+            # n_pad] (key 0 sits at position 0 of its quad-permuted group), -0 -> +0 on the bit pattern (0x8000 in both 16-bit types)
+            bits = Vn.view(self.depth, H, Vn.shape[2], Vn.shape[3])[:, :, :dh, 0].view(torch.int16)
+            return torch.where(bits == -32768, 0, bits).reshape(self.depth, D).contiguous().view(dt)
 
         ride_state = {"on": False}
 
@@ -750,7 +770,6 @@ class DiT(nn.Module):
         # the compute waves of a loader-wave kernel touch the lines of a LATER GEMM's weights in front of their k-loop - to_q
         # carries cproj's weights, cproj proj's, fc1 fc2's, fc2 the next block's to_q - and the LayerNorms keep to their own bytes.
         wpf = int(self.weight_prefetch)
-        collapse = bool(self.collapse_null_cross_attention) and null_half
         blocks = pk["blocks"]
         # `fuse_ln` (round 4): every gated residual add of a block is followed by the LayerNorm + modulate of the next branch
         # (dit_crossattn.py:55-57) - of the next block after fc2, of the final layer after the last one - so both are requested
@@ -772,7 +791,7 @@ class DiT(nn.Module):
         # the LayerNorm fold (`fold_ln`): planned calls only - u / v come from the loop's tables, shared by all batch entries
         fold_uv = fcent = fpart = None
         prow = plan["row"] if plan is not None else None
-        if (prow is not None and fuse and not collapse and not (self.cfg_streams and null_half and ops.PROFILE is None)
+        if (prow is not None and fuse and not (self.cfg_streams and null_half and ops.PROFILE is None)
                 and plan["t"].numel() <= self.fold_max_steps and self._fold_ok(T, N)):
             fold_uv = self._fold_tables(plan, dt, pk)["uv"]
             if dt == torch.float16:
@@ -781,6 +800,11 @@ class DiT(nn.Module):
             if wk not in self._fold_ws:
                 self._fold_ws = {wk: ops.fold_workspace(T, D, dev)}
             fcent, fpart = self._fold_ws[wk]
+        # (the round-3 opt-in: unfolded forwards that do not already skip)
+        collapse = bool(self.collapse_null_cross_attention) and null_half and fold_uv is None and not skip
+        # the skip's GEMM forms are whole row tiles: the unconditional rows start at a tile boundary of either tile
+        if skip and fold_uv is not None and (B * N) % 256:
+            skip = False
 
         fside: Dict[int, int] = {}                       # per row range (its b0): which of the fold's two (centre, scale) arrays the current site reads
 
@@ -789,6 +813,49 @@ class DiT(nn.Module):
 
         def carry(wt):
             return wt if wpf == 2 else None
+
+        def fold_call(with_kv: bool):
+            # the arguments of primx_dit_blocks_fold: this forward's struct and the per-block descriptors (built once per planned loop)
+            fd = plan["fold"]
+            dkey = (Kc.data_ptr(), Vc.data_ptr(), Kn_blk[0].data_ptr() if dedup else 0, wpf, Bkv)
+            if fd.get("desc_key") != dkey:
+                arr = (_lib.DitBlockFold * self.depth)()
+                rng = lambda t: ops._range(t) if wpf == 2 else (None, 0)
+                for i, w in enumerate(blocks):
+                    d = arr[i]
+                    for name in ("w_q", "b_q", "w_cproj", "b_cproj", "w_qkv", "w_proj", "b_proj", "w_fc1", "w_fc2", "b_fc2"):
+                        setattr(d, name, None if w[name] is None else w[name].data_ptr())
+                    d.Kc, d.Vc = Kc_blk[i].data_ptr(), Vc_blk[i].data_ptr()
+                    d.Kb, d.Vb = (Kn_blk[i].data_ptr(), Vn_blk[i].data_ptr()) if dedup else (None, None)
+                    d.uv_q = None if fold_uv[i][0] is None else fold_uv[i][0].data_ptr()
+                    d.uv_qkv, d.uv_fc1 = fold_uv[i][1].data_ptr(), fold_uv[i][2].data_ptr()
+                    for cname, t in (("carry_q", w["w_cproj"]), ("carry_cproj", w["w_proj"]), ("carry_fc1", w["w_fc2"]),
+                                     ("carry_fc2", blocks[i + 1]["w_q"] if i + 1 < self.depth else None)):
+                        cp, cn = rng(t) if t is not None else (None, 0)
+                        setattr(d, cname, cp)
+                        setattr(d, cname + "_bytes", cn)
+                fd["desc"], fd["desc_key"] = arr, dkey
+            f = _lib.DitForwardFold(
+                dtype=ops.dtype_code(dt), Be=Be, N=N, D=D, H=H, dh=dh, hidden=hid.shape[1], depth=self.depth, L=L, nq_pad=nq_pad,
+                nkv_pad_c=Kc.shape[2], nkv_pad_b=Kn_blk[0].shape[2] if dedup else 0, b_from=B if dedup else Be, step=prow,
+                n_steps=plan["t"].numel(), ln_eps=self.LN_EPS, scale=scale, h=h.data_ptr(), xn=xn.data_ptr(), att=att.data_ptr(),
+                hid=hid.data_ptr(), Qc=Qc.data_ptr(), Qs=Qs.data_ptr(), Ks=Ks.data_ptr(), Vs=Vs.data_ptr(), mod=mod.data_ptr(),
+                center0=fcent[0].data_ptr(), center1=fcent[1].data_ptr(), part=fpart.data_ptr())
+            if with_kv:
+                f.kv_A, f.kv_W, f.kv_bias = y16.data_ptr(), pk["w_kv_all"].data_ptr(), pk["b_kv_all"].data_ptr()
+                f.kv_rows, f.kv_rows_per_batch, f.kv_K = Bkv * Lk, Lk, Dc
+            if skip:
+                f.null_vrow = cs["vrow"].data_ptr()
+            return f, fd["desc"]
+
+        def single_launch(which: int, i: int, side: int, tag: str, flops: float) -> None:
+            # the skip's form of block i's to_q (1) or cross proj (2), which have no entry point of their own: ONE launch through
+            # primx_dit_blocks_fold (PrimxDitForwardFold::only_launch) - what the one-call route issues for that step
+            f, desc = fold_call(False)
+            f.only_block, f.only_launch, f.side = i, which, side
+            ops._dev(h, "h", torch.float32)
+            ops._timed(tag, flops, lambda: _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), desc, ops._stream()),
+                                                      "primx_dit_blocks_fold"))
 
         def block(i, w, b0, b1, hook=None):
             """DiTBlock i on batch entries [b0, b1) (dit_crossattn.py:51-58): 11 launches on the current stream, 8 with the LayerNorm fold."""
@@ -821,9 +888,12 @@ class DiT(nn.Module):
                 if folded:
                     fside[b0] = 0
                     ops.row_stats(hh, self.LN_EPS, fc_in())   # (centre, scale) of the first folded site: this LayerNorm's (mean, rstd)
-            bc = min(b1, B) if collapse else b1          # batch entries [b0, bc) attend; [bc, b1) are unconditional rows
+            bc = min(b1, B) if (collapse or skip) else b1   # batch entries [b0, bc) attend; [bc, b1) are unconditional rows
             if bc > b0:
-                if folded and i > 0:                     # (folded: bc == b1, every row attends)
+                if folded and i > 0 and skip:            # (the consumer over the attending rows; it finishes the other rows' statistics)
+                    single_launch(1, i, fside[b0], f"None {(bc - b0) * N}x{D}x{D}", 2.0 * (bc - b0) * N * D * D)
+                    fside[b0] ^= 1
+                elif folded and i > 0:                   # (bc == b1, every row attends)
                     ops.linear_heads_fold(xh, w["w_q"], N, H, dh, [HEADS_ROWS], [Qc[b0:bc]], nq_pad, fp, *uv(0), fc_in(), fc_flip(),
                                           self.LN_EPS, scale0=scale, carry=carry(w["w_cproj"]))
                 else:
@@ -835,7 +905,9 @@ class DiT(nn.Module):
                                   bcast=(Kn_blk[i], Vn_blk[i]))
                 else:
                     ops.attention(Qc[b0:bc], Kc_blk[i][b0:bc], Vc_blk[i][b0:bc], N, L, dh, scale, out=ah[:bc - b0])
-            if bc < b1:
+            if bc < b1 and skip and not folded:          # (unfolded: the value row is copied into the unconditional rows of `att`)
+                ah[max(bc, b0) - b0:].copy_(cs["vrow"][i].view(1, 1, D).expand(b1 - max(bc, b0), N, -1))
+            elif bc < b1 and not skip:
                 # V^T layout [b, h, DP, n_pad] (key 0 sits at position 0 of its quad-permuted group): the value row of every head
                 nb = b1 - max(bc, b0)
                 vsrc = Vn_blk[i].expand(nb, -1, -1, -1) if dedup else Vc_blk[i][max(bc, b0):b1]
@@ -843,7 +915,9 @@ class DiT(nn.Module):
                 ah[max(bc, b0) - b0:].copy_(vrow.expand(-1, N, -1))
             if hook is not None:
                 hook()
-            if folded:                                   # producer of the qkv site
+            if folded and skip:                          # producer of the qkv site; the unconditional rows of A are the value row
+                single_launch(2, i, fside[b0], f"None {Th}x{D}x{D}", 2.0 * Th * D * D)
+            elif folded:                                 # producer of the qkv site
                 ops.linear_gate_residual_fold(ah.view(Th, D), w["w_cproj"], w["b_cproj"], ch[2], hh, N, ch[4], fc_in(), xh, fp,
                                               carry=carry(w["w_proj"]))
             else:
@@ -887,7 +961,6 @@ class DiT(nn.Module):
                 ops.linear_gate_residual(hid[r0:r1], w["w_fc2"], w["b_fc2"], ch[8], hh, N,
                                          carry=None if last else carry(blocks[i + 1]["w_q"]), ln=ln_of(*nxt))
 
-        two_streams = bool(self.cfg_streams and null_half and self.depth and ops.PROFILE is None)
         one_call = (not two_streams and fold_uv is not None and self.blocks_call and sync is None and ops.PROFILE is None
                     and self.block_probe is None and _lib.blocks_call_available())
         # `kv_ride`: every folded single-stream forward - the library issues the riders on the one-call route, the block loop below otherwise
@@ -900,7 +973,12 @@ class DiT(nn.Module):
             project_kv(not ride)
             if ride_state["on"]:
                 ops.linear_heads_fold_pair(None, *kv_problem(0))     # block 0's projection: a launch of its own, on the riders' tile kernel
-        if self.cfg_streams and null_half and self.depth and ops.PROFILE is None:
+        if skip and cs.get("vrow") is None:
+            # ONCE per conditioning state, behind the broadcast entry's first projection: the rows depend on the null embedding and
+            # the packed to_v weights only, which live exactly as long as `cs` does (`null16` above; repack() drops both) - every
+            # later forward of the loop re-projects the same bits into Vn and launches nothing here
+            cs["vrow"] = null_value_rows()
+        if two_streams:
             # Two HIP streams, one per CFG half (the conditional and the unconditional rows are independent chains of
             # kernels): every GEMM of this path ends with a write burst that nothing of ITS OWN kernel can overlap
             # (DESIGN_LOG.md section 4); with the second chain a few kernels behind the first, one chain's burst drains
@@ -920,36 +998,9 @@ class DiT(nn.Module):
             # ONE foreign call for the forward's blocks (primx_dit_blocks_fold, ABI 24): the C side issues the launches block() below
             # would - same entry points, same arguments, same order, bit-identical results - at ~1 us of host time each instead of
             # ~21 us of Python + ctypes (tools/host_bound_check.py).  The per-block descriptors are built once per planned loop.
-            fd = plan["fold"]
-            dkey = (Kc.data_ptr(), Vc.data_ptr(), Kn_blk[0].data_ptr() if dedup else 0, wpf, Bkv)
-            if fd.get("desc_key") != dkey:
-                arr = (_lib.DitBlockFold * self.depth)()
-                rng = lambda t: ops._range(t) if wpf == 2 else (None, 0)
-                for i, w in enumerate(blocks):
-                    d = arr[i]
-                    for name in ("w_q", "b_q", "w_cproj", "b_cproj", "w_qkv", "w_proj", "b_proj", "w_fc1", "w_fc2", "b_fc2"):
-                        setattr(d, name, None if w[name] is None else w[name].data_ptr())
-                    d.Kc, d.Vc = Kc_blk[i].data_ptr(), Vc_blk[i].data_ptr()
-                    d.Kb, d.Vb = (Kn_blk[i].data_ptr(), Vn_blk[i].data_ptr()) if dedup else (None, None)
-                    d.uv_q = None if fold_uv[i][0] is None else fold_uv[i][0].data_ptr()
-                    d.uv_qkv, d.uv_fc1 = fold_uv[i][1].data_ptr(), fold_uv[i][2].data_ptr()
-                    for cname, t in (("carry_q", w["w_cproj"]), ("carry_cproj", w["w_proj"]), ("carry_fc1", w["w_fc2"]),
-                                     ("carry_fc2", blocks[i + 1]["w_q"] if i + 1 < self.depth else None)):
-                        cp, cn = rng(t) if t is not None else (None, 0)
-                        setattr(d, cname, cp)
-                        setattr(d, cname + "_bytes", cn)
-                fd["desc"], fd["desc_key"] = arr, dkey
-            f = _lib.DitForwardFold(
-                dtype=ops.dtype_code(dt), Be=Be, N=N, D=D, H=H, dh=dh, hidden=hid.shape[1], depth=self.depth, L=L, nq_pad=nq_pad,
-                nkv_pad_c=Kc.shape[2], nkv_pad_b=Kn_blk[0].shape[2] if dedup else 0, b_from=B if dedup else Be, step=prow,
-                n_steps=plan["t"].numel(), ln_eps=self.LN_EPS, scale=scale, h=h.data_ptr(), xn=xn.data_ptr(), att=att.data_ptr(),
-                hid=hid.data_ptr(), Qc=Qc.data_ptr(), Qs=Qs.data_ptr(), Ks=Ks.data_ptr(), Vs=Vs.data_ptr(), mod=mod.data_ptr(),
-                center0=fcent[0].data_ptr(), center1=fcent[1].data_ptr(), part=fpart.data_ptr())
-            if ride:
-                f.kv_A, f.kv_W, f.kv_bias = y16.data_ptr(), pk["w_kv_all"].data_ptr(), pk["b_kv_all"].data_ptr()
-                f.kv_rows, f.kv_rows_per_batch, f.kv_K = Bkv * Lk, Lk, Dc
+            f, desc = fold_call(ride)
             ops._dev(h, "h", torch.float32)                 # (the launch-device check of every op: ops._stream)
-            _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), fd["desc"], ops._stream()), "primx_dit_blocks_fold")
+            _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), desc, ops._stream()), "primx_dit_blocks_fold")
         else:
             for i, w in enumerate(pk["blocks"]):
                 block(i, w, 0, Be)

@@ -392,6 +392,23 @@ typedef struct PrimxDitForwardFold {
      * (primx_linear_heads_fold_pair).  kv_A == NULL: the caller has filled Kc / Vc. */
     const void *kv_A, *kv_W, *kv_bias;
     int kv_rows, kv_rows_per_batch, kv_K;
+    /* The null cross-attention skip (added to version 35 without a new number: a zeroed tail is the call as it was, and a library from
+     * before ignores the tail and computes the same results the long way).  null_vrow != NULL - needs 0 < b_from and Be == 2 b_from: the
+     * batch entries [b_from, Be) attend to L copies of ONE key / value row, so the cross-attention output of every one of their rows is
+     * that value row of each head, bit for bit, whatever the query (finite scores; a -0 of the value row comes out as +0 -
+     * tests/test_hip_null_identity.py), and to_q and the attention walk of those entries compute nothing else.  With it
+     *   to_q runs over the rows of the entries [0, b_from) only; its column tile 0 workgroups also finish the LayerNorm-fold
+     *     statistics of the other half's rows (same formula, same bits as the launch over all rows wrote);
+     *   the cross-attention is primx_attention over the entries [0, b_from) (Kc / Vc; Kb / Vb are not read);
+     *   the cross proj reads, for the rows of the entries [b_from, Be), ONE row as every row of its A operand: block i's
+     *     null_vrow[i * D .. i * D + D) = the value row of the H heads side by side, -0 replaced by +0 (16-bit, 16-byte aligned).
+     *     `att` rows of those entries are neither written nor read.
+     * Everything else - and every result - is the call without it.
+     * only_launch != 0: issue ONE launch of block `only_block` in this form and nothing else - 1 = to_q (only_block >= 1), 2 = the cross
+     * proj; `side` = which of center0 / center1 that launch's site reads.  (How a host that issues the other launches itself, one by one -
+     * per-launch timing - gets at the two launches that have no entry point of their own.) */
+    const void* null_vrow;
+    int only_block, only_launch, side;
 } PrimxDitForwardFold;
 
 /* The `depth` DiT blocks of a forward whose LayerNorms are folded (every call below is one of this header's entry points, issued
@@ -404,6 +421,9 @@ typedef struct PrimxDitForwardFold {
  *   ->  primx_linear_gate_residual_fold (fc2; last block: primx_linear_gate_residual_ln with the final layer's shift / scale).
  * Replaces the loop `for block in self.blocks: x = block(x, y, c)` (models/dit_crossattn.py:198-199) of a planned sampling loop. */
 int primx_dit_blocks_fold(const PrimxDitForwardFold* f, const PrimxDitBlockFold* blocks, void* stream);
+/* Which tail fields of PrimxDitForwardFold this library reads (bit 0: null_vrow, only_block, only_launch, side - the null
+ * cross-attention skip).  A build of version 35 from before the skip lacks the symbol. */
+int primx_dit_blocks_fold_features(void);
 
 /* Gather a [B, M, H, dh] tensor with arbitrary element strides (the xFormers BMHK operand, e.g.
  * a view into the fused qkv buffer) into an attention operand layout. */
