@@ -79,6 +79,8 @@ SIGNATURES = {
     "primx_linear_heads": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_p), _i, _i, _i, _f, _i, _p, _l, _p],
     "primx_attention": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],
     "primx_attention_bcast": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _i, _i, _i, _p],
+    "primx_attention_ksplit_mode": [_i],
+    "primx_attention_ksplit": [_i, _i, _i, _i],
     "primx_pack_heads": [_p, _l, _l, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "primx_cfg_combine": [_p, _p, _i, _l, _f, _p],
     "primx_diffusion_step": [_p, _p, _i, _l, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
@@ -164,7 +166,9 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # refinement entry points (_REFINE_ENTRY_POINTS: a version-33 build serves everything but the differentiable PrimSDF and refine=);
 # version 35 added primx_raymarch_backward (_RAYMARCH_GRAD_ENTRY_POINTS: a version-34 build serves everything but the marcher's backward);
 # primx_material_sample (_MATERIAL_ENTRY_POINTS) was added to version 35 without a new number, because it changes no existing call: an
-# A/B build of version 35 from before it lacks the symbol and serves everything but a MeshField with a material
+# A/B build of version 35 from before it lacks the symbol and serves everything but a MeshField with a material;
+# the attention key split's switch and query (_ATTN_KSPLIT_ENTRY_POINTS) joined version 35 the same way: a build from before them
+# never splits (`attn_ksplit_available()`)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
@@ -182,12 +186,14 @@ _FIT_ENTRY_POINTS: set = {"primx_mesh_field_query", "primx_mesh_face_areas", "pr
 _REFINE_ENTRY_POINTS: set = {"primx_primsdf_query_backward", "primx_adam_step"}
 _RAYMARCH_GRAD_ENTRY_POINTS: set = {"primx_raymarch_backward"}
 _MATERIAL_ENTRY_POINTS: set = {"primx_material_sample"}
+_ATTN_KSPLIT_ENTRY_POINTS: set = {"primx_attention_ksplit_mode", "primx_attention_ksplit"}
 _AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34)
 _fold_available: dict = {}
 _blocks_call: dict = {}
 _kv_ride: dict = {}
 _f32out_group: dict = {}
 _null_skip: dict = {}
+_attn_ksplit: dict = {}
 
 _lib: Optional[C.CDLL] = None
 
@@ -255,7 +261,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
             continue
         if got < 35 and name in _RAYMARCH_GRAD_ENTRY_POINTS:
             continue
-        if ab and (name in _MATERIAL_ENTRY_POINTS or name == "primx_dit_blocks_fold_features") and not hasattr(lib, name):
+        if ab and (name in _MATERIAL_ENTRY_POINTS or name in _ATTN_KSPLIT_ENTRY_POINTS or name == "primx_dit_blocks_fold_features") and not hasattr(lib, name):
             continue                # an A/B build from before the entry point existed (same version number)
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
@@ -265,6 +271,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     _kv_ride[path] = got >= 25
     _f32out_group[path] = got >= 26
     _null_skip[path] = got >= 35 and hasattr(lib, "primx_dit_blocks_fold_features") and bool(lib.primx_dit_blocks_fold_features() & 1)
+    _attn_ksplit[path] = hasattr(lib, "primx_attention_ksplit")
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -299,6 +306,12 @@ def null_skip_available() -> bool:
     for a PRIMX_LIB A/B build from before it; same version number, told apart by primx_dit_blocks_fold_features.)"""
     load()
     return _null_skip.get(LIB_PATH, False)
+
+
+def attn_ksplit_available() -> bool:
+    """Does the loaded library carry the attention key split and its switch?  (False only for an older PRIMX_LIB A/B build.)"""
+    load()
+    return _attn_ksplit.get(LIB_PATH, False)
 
 
 def check(status: int, name: str) -> None:

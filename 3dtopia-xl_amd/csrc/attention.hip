@@ -14,6 +14,10 @@
 // PRIMX_HEADS_VT layout stores V^T with the 4-key quads of every 16 keys in the order {0,2,1,3}, which
 // makes the 8 keys a lane owns in one 16-key MFMA step a contiguous 16-byte LDS read - P never
 // leaves registers and needs no permute.
+// A launch that would give a workgroup to at most half of the CUs (the rule in primx_attention_bcast: cross-attention at batch 1,
+// DINOv2's attention) runs the KSPLIT form instead: 128 query rows per workgroup, waves w and w + 4 own the SAME 32 queries, the
+// wave group 0-3 walks the first half of the key tiles and the group 4-7 the second, and group 0 merges the two partial
+// (O, max, row sum) through LDS behind the loop - twice the workgroups, half the tiles each, the ping-pong unchanged.
 //
 // Staging is LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction) into a 3-stage ring shared by all 8 waves:
 // no staging VGPRs, no ds_write.  The GLOBAL layouts are designed for it: K rows are stored with the padded stride
@@ -21,6 +25,8 @@
 // 16-byte-slot row stride that makes ds_read_b128 conflict-free; V^T tiles (DP rows x 128 B) land in unpadded
 // 128-byte LDS rows with the chunk index XOR-swizzled by ((row>>1)&7), applied on the per-lane SOURCE address.
 // Stage j % 3 holds the PAIR {K(j+1), V(j)}: K runs one tile ahead of V (scores double-buffered in registers).
+// KSPLIT: each wave group has a ring of its own (2 x 70,656 B at dh = 72, still one workgroup per CU) that its four waves fill -
+// two copy the K pieces, two the V^T pieces, 6 DMAs per wave and pair instead of 3 - and only they read.
 //
 // Schedule ("ping-pong", MI355X_MICROARCH.md "Two waves per SIMD"): a step of a wave is a LIGHT segment L - DMA issue,
 // all LDS fragment reads of the step's first MFMAs, row max / rare rescale - and a MATRIX segment M - 22 MFMAs with
@@ -64,7 +70,11 @@ __device__ __forceinline__ V8 ldg16(const void* ptr) {
 // switches until round 4; their measurements are in DESIGN_LOG.md section 5.)
 __device__ unsigned long long g_attn_prof[8];
 
-template <int DT, int KSTEPS, int DTILES, int KMASK, int PROF = 0>
+// KSPLIT = 1 (launches that would leave half of the CUs empty, primx_attention_bcast's rule): the workgroup takes 128 query rows
+// instead of 256 and its two wave groups walk the first and the second half of the key tiles for the SAME queries, each through a
+// ring of its own; the two partial results meet in LDS behind the main loop ("merge" below).  KSPLIT = 0 is the kernel as described
+// above: every line the split adds is behind `if constexpr (KSPLIT)` or a ternary on it.
+template <int DT, int KSTEPS, int DTILES, int KMASK, int PROF = 0, int KSPLIT = 0>
 __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>::S* __restrict__ Qp,
                                                           const typename T16<DT>::S* __restrict__ Kp,
                                                           const typename T16<DT>::S* __restrict__ Vt,
@@ -86,13 +96,21 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     constexpr int NK = KT / 512;               // DMA wave-instructions per K tile   (11 / 9 / 5 for dh 72 / 64 / 32)
     constexpr int NV = DP / 8;                 // per V^T tile, 8 rows each          (10 / 8 / 4)
     constexpr int HW = NW / 2;                 // waves per group = per DMA role (group 0: K pieces, group 1: V^T pieces)
-    constexpr int NSLOT = ((NK > NV ? NK : NV) + HW - 1) / HW;   // DMAs per wave per pair
+    constexpr int RWV = KSPLIT ? HW / 2 : HW;  // waves per DMA role and ring (KSPLIT: two of a group's four waves copy K, two V^T)
+    constexpr int NSLOT = ((NK > NV ? NK : NV) + RWV - 1) / RWV;   // DMAs per wave per pair
+    constexpr int NRING = KSPLIT ? 2 : 1;      // KSPLIT: one ring per wave group
+    constexpr int BQK = KSPLIT ? BQ / 2 : BQ;  // query rows per workgroup
     static_assert(KT % 512 == 0, "K tile must be whole DMA instructions");
-    __shared__ __attribute__((aligned(16))) S smem[NSTAGE * BUF];
+    static_assert(NSLOT * (NSTAGE - 2) <= 63, "the DMAs in flight must fit the 6-bit vmcnt field");
+    __shared__ __attribute__((aligned(16))) S smem[NRING * NSTAGE * BUF];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave / HW, rw = wave % HW;                                  // wave-uniform
+    // KSPLIT: waves w and w + 4 own the same 32 queries; inside a group waves 0, 1 copy the K pieces and waves 2, 3 the V^T pieces
+    const int wq = KSPLIT ? rw : wave;                                          // the wave's 32-row slice of the query tile
+    const int role = KSPLIT ? rw / RWV : grp, rk = KSPLIT ? rw % RWV : rw;      // DMA role (0: K, 1: V^T) and rank among its waves
+    const int ring = KSPLIT ? grp * (NSTAGE * BUF) : 0;                         // offset of the ring this wave fills and reads
     const int l31 = lane & 31, hi = lane >> 5;
     // Workgroup id -> (batch-head, query tile).  Ids go round-robin over the 8 XCDs, so with B*H % 8 == 0 all query tiles of a head share
     // an XCD's L2 whatever the order - but the ORDER decides whether its K / V^T (0.7 MB at 2048 keys) are still there for the next query
@@ -106,7 +124,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
         qt = l - j * (int)gridDim.y;
         bh = (id & 7) + 8 * j;
     }
-    const int q0 = qt * BQ;
+    const int q0 = qt * BQK;
     // Batch entries >= b_from attend to nkv COPIES OF ONE key / value row (primx_attention_bcast: the unconditional half of
     // classifier-free guidance, whose conditioning tokens are one embedding expanded to the sequence length).  Their operands
     // hold that sequence once - tile 0 = 64 copies, tile 1 = the ragged last tile (nkv % 64 keys, the rest masked like any
@@ -121,7 +139,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     if (VR > DP) {
         for (int i = tid; i < (VR - DP) * 64; i += 64 * NW) {
 #pragma unroll
-            for (int stg = 0; stg < NSTAGE; ++stg) smem[stg * BUF + KT + DP * 64 + i] = (S)0.f;
+            for (int stg = 0; stg < NRING * NSTAGE; ++stg) smem[stg * BUF + KT + DP * 64 + i] = (S)0.f;
         }
     }
 
@@ -137,7 +155,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     // of the first MFMA of every launch)
     V8 qf[KSTEPS];
     auto load_q = [&]() {
-        const S* qrow = Qp + ((int64_t)bh * nq_pad + min(q0 + wave * 32 + l31, nq_pad - 1)) * DP + hi * 8;
+        const S* qrow = Qp + ((int64_t)bh * nq_pad + min(q0 + wq * 32 + l31, nq_pad - 1)) * DP + hi * 8;
 #pragma unroll
         for (int s = 0; s < KSTEPS; ++s) qf[s] = ldg16<V8>(qrow + s * 16);
         if (QCOL) {
@@ -167,16 +185,20 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     // clamped, so EVERY wave issues exactly NSLOT DMAs per pair with scalar-only address arithmetic - no branches, and
     // the vmcnt bookkeeping is static: "vmcnt(NSLOT)" = everything older than the newest pair has landed.
     const int ntiles = (nkv + BKV - 1) / BKV;
-    const int n_pc = grp ? NV : NK, per = (n_pc + HW - 1) / HW;
-    const int run_first = min(rw * per, n_pc - 1);
-    const int run_len = max(min(per, n_pc - rw * per), 1);
-    const int64_t piece_stride = grp ? (int64_t)8 * kvp : 512;                  // halves between consecutive pieces
-    const int tile_stride = grp ? BKV : KT;
-    const S* role_base = grp ? Vbase : Kbase;
+    // KSPLIT: group 0 walks the tiles [0, h), group 1 the tiles [h, ntiles) with h = ceil(ntiles / 2) - the ragged last tile (and
+    // its KMASK overwrite) is group 1's.  Tile indices stay GLOBAL everywhere below (tile_at, the key mask, the pair numbers).
+    const int jbeg = KSPLIT ? (grp ? (ntiles + 1) / 2 : 0) : 0;
+    const int jend = KSPLIT ? (grp ? ntiles : (ntiles + 1) / 2) : ntiles;
+    const int n_pc = role ? NV : NK, per = (n_pc + RWV - 1) / RWV;
+    const int run_first = min(rk * per, n_pc - 1);
+    const int run_len = max(min(per, n_pc - rk * per), 1);
+    const int64_t piece_stride = role ? (int64_t)8 * kvp : 512;                 // halves between consecutive pieces
+    const int tile_stride = role ? BKV : KT;
+    const S* role_base = role ? Vbase : Kbase;
     const int v_lrow = lane >> 3, v_lc = lane & 7;
     // per-lane source offset inside a piece; for V^T it depends on the parity of the 8-row group (swizzle term 4*tv & 7)
-    const int lane_off0 = grp ? v_lrow * kvp + ((v_lc ^ ((v_lrow >> 1) & 7)) * 8) : lane * 8;
-    const int lane_off1 = grp ? v_lrow * kvp + ((v_lc ^ ((4 + (v_lrow >> 1)) & 7)) * 8) : lane * 8;
+    const int lane_off0 = role ? v_lrow * kvp + ((v_lc ^ ((v_lrow >> 1) & 7)) * 8) : lane * 8;
+    const int lane_off1 = role ? v_lrow * kvp + ((v_lc ^ ((4 + (v_lrow >> 1)) & 7)) * 8) : lane * 8;
     const bool ragged = (nkv & (BKV - 1)) != 0;
     auto tile_at = [&](int tile) {            // tile index inside this entry's operand buffers (uniform)
         const int tl = min(tile, ntiles - 1);
@@ -188,10 +210,10 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
         for (int i = 0; i < NSLOT; ++i) {
             const int pc = run_first + min(i, run_len - 1);
             const S* src = tb + pc * piece_stride + ((pc & 1) ? lane_off1 : lane_off0);
-            __builtin_amdgcn_global_load_lds((GV*)(uintptr_t)src, (LV*)(smem + stage * BUF + (grp * NK + pc) * 512), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((GV*)(uintptr_t)src, (LV*)(smem + ring + stage * BUF + (role * NK + pc) * 512), 16, 0, 0);
         }
     };
-    [[maybe_unused]] auto issue_pair = [&](int jp, int stage) { issue_run(jp + 1 - grp, stage); };   // {K(jp+1), V(jp)}
+    [[maybe_unused]] auto issue_pair = [&](int jp, int stage) { issue_run(jp + 1 - role, stage); };   // {K(jp+1), V(jp)}
 
     f32x16 o[DTILES];
 #pragma unroll
@@ -206,14 +228,14 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     // ---- LDS fragment reads: batched, each batch consumed after ONE wait (builtin s_waitcnt: hipcc's own waitcnt
     // pass sees it and does not add a second, stricter wait in front of the consumers)
     auto read_k = [&](int stage, V8 (&kf)[2][KSTEPS]) {
-        const S* kb = smem + stage * BUF + l31 * KROW + hi * 8;
+        const S* kb = smem + ring + stage * BUF + l31 * KROW + hi * 8;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int s = 0; s < KSTEPS; ++s) kf[kt][s] = *reinterpret_cast<const V8*>(kb + kt * 32 * KROW + s * 16);
     };
     auto read_v = [&](int stage, int half, V8 (&vf)[DTILES][2]) {   // key-steps 2*half, 2*half+1 of the tile
-        const S* vb = smem + stage * BUF + KT + l31 * 64;
+        const S* vb = smem + ring + stage * BUF + KT + l31 * 64;
         const int sw = (l31 >> 1) & 7;                                // rows t*32 + l31: (row>>1)&7 does not depend on t
 #pragma unroll
         for (int t = 0; t < DTILES; ++t)
@@ -297,7 +319,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     // The barrier BEHIND a light segment.  The DMA of the next pair is issued in the MATRIX segment: nothing was issued since the previous matrix segment, and what that one
     // issued is read by the OTHER group's next light segment, which starts behind this very barrier - everything must
     // have landed (a first build waited vmcnt(NFLY) here too: stale tiles, NaNs on some launches).
-    constexpr int NFLY_L = 0;
+    // (KSPLIT: a ring has no other group.  What the previous matrix segment issued - pair j+1 - is first read in this group's
+    // L(j+1), behind the vmcnt(NFLY) barrier that follows M(j): nothing has to land here.)
+    constexpr int NFLY_L = KSPLIT ? NSLOT : 0;
     unsigned long long pt = 0, pl = 0, pm = 0, pw = 0, pn = 0, pl_dma = 0, pl_rd = 0;
     auto stamp = [&](unsigned long long& acc) {
         if (PROF) {
@@ -414,9 +438,9 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     };
 
     // ---- prologue: K(0) parks in the last stage, pairs 0 and 1 are issued; S(0) = K(0) Q^T
-    if (!grp) issue_run(0, NSTAGE - 1);
+    if (!role) issue_run(jbeg, NSTAGE - 1);
 #pragma unroll
-    for (int pr = 0; pr < NSTAGE - 1; ++pr) issue_pair(pr, pr);
+    for (int pr = 0; pr < NSTAGE - 1; ++pr) issue_pair(jbeg + pr, pr);
     load_q();
     if (QCOL) set_q_cols(0.f);
     f32x16 sA[2], sB[2];
@@ -426,7 +450,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
         read_k(NSTAGE - 1, kf0);
         fence_lds();
         asm volatile("s_barrier" ::: "memory");   // group 0's L(0) refills this stage: everyone's K(0) reads are home first
-        qk(kf0, 0, sA);                   // S(0)
+        qk(kf0, jbeg, sA);                // S(0)
     }
     if (PROF) pt = __builtin_readcyclecounter();
     // ---- main loop.  Group 0 runs  L B M B,  group 1 runs  B L B M  per step: the same number of barriers, group 1 half
@@ -434,12 +458,20 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     // group 1's L(j-1) and whose V^T part in group 1's M(j-1) - both behind a barrier that precedes the issuing
     // segment (group 0 issues K pieces in its L(j), group 1 V^T pieces in its L(j)); pair j is complete before the
     // barrier in front of group 0's L(j) because every wave waits vmcnt(NSLOT) before EVERY barrier.
+    // KSPLIT: the barrier pattern is the same, but a ring is filled and read by ONE group's four waves, each walking its own
+    // tiles j in [jbeg, jend).  Pair j+2 is issued in the group's M(j) into the stage of pair j-1; all LDS reads of that stage
+    // (K part and both V^T halves) are issued in the group's L(j-1) and are home (lgkmcnt(0)) before the barrier behind it, which
+    // every wave of the group passes before any of them enters M(j-1), let alone M(j).  Pair j is read first in L(j): each wave
+    // waited vmcnt(NSLOT) - everything but the newest pair, j+1 - for its own pieces before the barrier in front of L(j) (behind
+    // M(j-1) for group 0).  Every wave still waits for its own pieces before every barrier, so the rule needs no case for which
+    // group a barrier "belongs" to.  With an odd tile count group 1 has one tile fewer and passes the two barriers of the
+    // missing step bare, behind its loop.
     int st = 0, st_free = NSTAGE - 1;
     V8 kf[2][KSTEPS], vf0[DTILES][2], vf1[DTILES][2];
-    int j = 0;
-    for (; j + 1 < ntiles; j += 2) {
+    int j = jbeg;
+    for (; j + 1 < jend; j += 2) {
         if (grp) { PRIMX_ATTN_WAITB(); stamp(pw); }
-        seg_light(st, st_free, j + NSTAGE - 1, sA, kf, vf0, vf1, j == 0);
+        seg_light(st, st_free, j + NSTAGE - 1, sA, kf, vf0, vf1, j == jbeg);
         stamp(pl);
         PRIMX_ATTN_WAITB_N(NFLY_L);
         stamp(pw);
@@ -460,12 +492,18 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
         st = (st == NSTAGE - 1) ? 0 : st + 1;
         if (PROF) pn += 2;
     }
-    if (j < ntiles) {                     // odd tile count (the DMAs are clamped and redundant: uniform vmcnt bookkeeping)
+    if (j < jend) {                       // odd tile count (the DMAs are clamped and redundant: uniform vmcnt bookkeeping)
         if (grp) PRIMX_ATTN_WAITB();
-        seg_light(st, st_free, j + NSTAGE - 1, sA, kf, vf0, vf1, j == 0);
+        seg_light(st, st_free, j + NSTAGE - 1, sA, kf, vf0, vf1, j == jbeg);
         PRIMX_ATTN_WAITB_N(NFLY_L);
         seg_matrix(st, ntiles - 1, sA, sB, kf, vf0, vf1, j + NSTAGE - 1, st_free);
         if (!grp) PRIMX_ATTN_WAITB();
+    }
+    if constexpr (KSPLIT) {
+        if (grp && (ntiles & 1)) {        // group 0's last step has no partner: its two barriers, no arithmetic, no duplicate tile
+            asm volatile("s_barrier" ::: "memory");
+            asm volatile("s_barrier" ::: "memory");
+        }
     }
     __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0): drain the clamped tail DMAs before the workgroup retires
 #undef PRIMX_ATTN_WAITB
@@ -473,6 +511,37 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     if (PROF && lane == 0) {
         atomicAdd(&g_attn_prof[0], pl); atomicAdd(&g_attn_prof[1], pm); atomicAdd(&g_attn_prof[2], pw);
         atomicAdd(&g_attn_prof[3], pn); atomicAdd(&g_attn_prof[4], pl_dma); atomicAdd(&g_attn_prof[5], pl_rd);
+    }
+
+    // ---- merge (KSPLIT): wave w (group 0) and wave w + 4 (group 1) hold, lane for lane, the partial O / max / row sum of the SAME
+    // queries over the two halves of the keys.  Group 1 parks its registers in ring 0 laid out [register][wave][lane] - every
+    // access is 64 consecutive floats - and group 0 folds them in:  m = max(m0, m1),  a_g = exp2(m_g - m) (exp2((m_g - m) c)
+    // where the scores are raw),  O = O0 a0 + O1 a1,  likewise the row sum (output row dh of O on the dh = 72 path).  a_g <= 1; both
+    // halves hold real keys (ntiles >= 16 by the launch rule), so no m_g is the initial -1e30 and neither a_g is 0 / 0.
+    if constexpr (KSPLIT) {
+        constexpr int NO = 16 * DTILES;
+        static_assert((NO + 2) * (64 * HW) * 4 <= NSTAGE * BUF * (int)sizeof(S), "the parked partial results must fit ring 0");
+        float* park = reinterpret_cast<float*>(smem) + rw * 64 + lane;
+        __syncthreads();                                  // every wave has left its ring, every tail DMA has landed
+        if (grp) {
+#pragma unroll
+            for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) park[(16 * t + r) * (64 * HW)] = o[t][r];
+            park[NO * (64 * HW)] = m_run;
+            if (KMASK) park[(NO + 1) * (64 * HW)] = l_run;
+        }
+        __syncthreads();
+        if (grp) return;                                  // group 0 meets no barrier from here on
+        const float m1 = park[NO * (64 * HW)];
+        const float m = fmaxf(m_run, m1);
+        const float a0 = __builtin_amdgcn_exp2f(QCOL ? m_run - m : (m_run - m) * c);
+        const float a1 = __builtin_amdgcn_exp2f(QCOL ? m1 - m : (m1 - m) * c);
+#pragma unroll
+        for (int t = 0; t < DTILES; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[t][r] = o[t][r] * a0 + park[(16 * t + r) * (64 * HW)] * a1;
+        if (KMASK) l_run = l_run * a0 + park[(NO + 1) * (64 * HW)] * a1;
     }
 
     // ---- epilogue: normalise and store out[b, q, h*dh + d]
@@ -492,7 +561,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
         l_tot = __shfl(lsum, l31 + 32 * ((rr >> 2) & 1));
     }
     const float inv = 1.0f / l_tot;
-    const int q = q0 + wave * 32 + l31;
+    const int q = q0 + wq * 32 + l31;
     const int b = bh / H, h = bh - b * H;
     // Row-major stores through LDS.  A lane owns one query row, so storing from the accumulators is 64 separate 8-byte
     // requests per instruction (9 instructions per wave at dh = 72, every wave at once at the end of the kernel); each wave
@@ -500,9 +569,11 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
     // consecutive lanes per output row.
     if ((dh & 7) == 0) {
         constexpr int OST = DP + 8;
-        static_assert(NW * 32 * OST <= NSTAGE * BUF, "output staging must fit the ring");
-        __syncthreads();                                  // every wave has left the ring
-        S* ost = smem + wave * (32 * OST);
+        static_assert((KSPLIT ? HW : NW) * 32 * OST <= NSTAGE * BUF, "output staging must fit the ring");
+        if constexpr (!KSPLIT) __syncthreads();           // every wave has left the ring
+        // (KSPLIT: only group 0 is here.  Its waves stage in ring 1, which group 1 left before the merge's barriers, while other
+        // waves of group 0 may still be reading the parked partial results out of ring 0.)
+        S* ost = smem + (KSPLIT ? NSTAGE * BUF : 0) + wq * (32 * OST);
 #pragma unroll
         for (int t = 0; t < DTILES; ++t)
 #pragma unroll
@@ -518,7 +589,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attn_kernel(const typename T16<DT>
         const int cpr = dh >> 3, npiece = 32 * cpr;       // 16-byte pieces per row / per wave tile
         for (int p = lane; p < npiece; p += 64) {
             const int row = p / cpr, c = p - row * cpr;
-            const int qr = q0 + wave * 32 + row;
+            const int qr = q0 + wq * 32 + row;
             if (qr < nq)
                 *reinterpret_cast<V8*>(out + ((int64_t)b * nq + qr) * ((int64_t)H * dh) + (int64_t)h * dh + 8 * c) =
                     *reinterpret_cast<const V8*>(ost + row * OST + 8 * c);
@@ -642,34 +713,73 @@ static const int g_attn_prof_on = [] {
     return e ? atoi(e) : 0;
 }();
 
+// PRIMX_ATTN_KSPLIT (read once at load): unset or "auto" = split the keys inside the workgroup where attn_ksplit() says so,
+// "0" = never.  primx_attention_ksplit_mode() sets the same switch in-process: -1 auto, 0 never, 1 wherever the kernel allows it.
+static int g_attn_ksplit_mode = [] {
+    const char* e = getenv("PRIMX_ATTN_KSPLIT");
+    return (e && e[0] == '0' && e[1] == 0) ? 0 : -1;
+}();
+
+static int attn_cu_count() {
+    static const int n_cu = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        return n;
+    }();
+    return n_cu;
+}
+
+// The rule.  Each half of the keys needs tiles enough to amortise the merge and to keep every running max a real one
+// (ntiles >= 16: at least 8 tiles each); and the split pays only where the 256-row workgroups would leave at least half of the
+// CUs without one.  b_from = the entries with keys of their own: the decision must not depend on whether the broadcast entries
+// ride in the same launch (tests/test_hip_null_skip.py compares the two routes bit for bit).
+static int attn_ksplit(int b_from, int H, int nq_pad, int nkv) {
+    const int ntiles = (nkv + BKV - 1) / BKV;
+    if (g_attn_ksplit_mode == 0 || ntiles < 16) return 0;
+    if (g_attn_ksplit_mode == 1) return 1;
+    return 2LL * b_from * H * ((nq_pad + BQ - 1) / BQ) <= attn_cu_count();
+}
+
 template <int DT, int KSTEPS, int DTILES, int KMASK>
 void launch_attn(const void* Qp, const void* Kp, const void* Vt, void* out, int B, int H, int nq, int nq_pad, int nkv,
-                 int nkv_pad, int dh, float c, const void* Kb, const void* Vb, int b_from, int nkv_pad_b, hipStream_t st) {
+                 int nkv_pad, int dh, float c, const void* Kb, const void* Vb, int b_from, int nkv_pad_b, int ksplit, hipStream_t st) {
     using S = typename T16<DT>::S;
-    dim3 grid(B * H, (nq_pad + BQ - 1) / BQ);
-#define PRIMX_ATTN_LAUNCH(P)                                                                                         \
-    hipLaunchKernelGGL((attn_kernel<DT, KSTEPS, DTILES, KMASK, P>), grid, dim3(64 * NW), 0, st, (const S*)Qp,         \
+    const int bq = ksplit ? BQ / 2 : BQ;
+    dim3 grid(B * H, (nq_pad + bq - 1) / bq);
+#define PRIMX_ATTN_LAUNCH(P, KS)                                                                                     \
+    hipLaunchKernelGGL((attn_kernel<DT, KSTEPS, DTILES, KMASK, P, KS>), grid, dim3(64 * NW), 0, st, (const S*)Qp,     \
                        (const S*)Kp, (const S*)Vt, (S*)out, H, nq, nq_pad, nkv, nkv_pad, dh, c, (const S*)Kb, (const S*)Vb,  \
                        b_from, nkv_pad_b)
     if constexpr (DT == PRIMX_F16 && KSTEPS == 5) {
         if (g_attn_prof_on) {
             unsigned long long z[8] = {0}, r[8];
             (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_prof), z, sizeof(z));
-            PRIMX_ATTN_LAUNCH(1);
+            if (ksplit) PRIMX_ATTN_LAUNCH(1, 1);
+            else PRIMX_ATTN_LAUNCH(1, 0);
             (void)hipStreamSynchronize(st);
             (void)hipMemcpyFromSymbol(r, HIP_SYMBOL(g_attn_prof), sizeof(r));
             const double n = r[3] ? (double)r[3] : 1.0;
-            fprintf(stderr, "attn segment profile (cycles per step per wave, %llu wave-steps): light %.0f (DMA issue %.0f, LDS read "
-                            "issue %.0f, max/rescale %.0f) | matrix %.0f | waits + barriers %.0f | total %.0f\n", r[3],
+            fprintf(stderr, "attn segment profile%s (cycles per step per wave, %llu wave-steps): light %.0f (DMA issue %.0f, LDS read "
+                            "issue %.0f, max/rescale %.0f) | matrix %.0f | waits + barriers %.0f | total %.0f\n", ksplit ? " [ksplit]" : "", r[3],
                     (r[0] + r[4] + r[5]) / n, r[4] / n, r[5] / n, r[0] / n, r[1] / n, r[2] / n, (r[0] + r[1] + r[2] + r[4] + r[5]) / n);
             return;
         }
     }
-    PRIMX_ATTN_LAUNCH(0);
+    if (ksplit) PRIMX_ATTN_LAUNCH(0, 1);
+    else PRIMX_ATTN_LAUNCH(0, 0);
 #undef PRIMX_ATTN_LAUNCH
 }
 
 }  // namespace
+
+extern "C" int primx_attention_ksplit_mode(int mode) {
+    const int was = g_attn_ksplit_mode;
+    g_attn_ksplit_mode = mode < 0 ? -1 : mode > 0 ? 1 : 0;
+    return was;
+}
+
+extern "C" int primx_attention_ksplit(int b_from, int H, int nq_pad, int nkv) { return attn_ksplit(b_from, H, nq_pad, nkv); }
 
 extern "C" int primx_attention(const void* Qp, const void* Kp, const void* Vt, void* out, int B, int H, int nq,
                                int nq_pad, int nkv, int nkv_pad, int dh, float scale, int dtype, void* stream) {
@@ -706,10 +816,11 @@ extern "C" int primx_attention_bcast(const void* Qp, const void* Kp, const void*
     PRIMX_REQUIRE(nq_pad / QPAD <= 65535, "primx_attention: too many query tiles");
     const float c = scale * 1.4426950408889634f;
     hipStream_t st = (hipStream_t)stream;
+    const int ks = attn_ksplit(b_from, H, nq_pad, nkv);
     PRIMX_DISPATCH_16(dtype, "primx_attention", {
-        if (dh == 72) launch_attn<DT, 5, 3, 0>(Qp, Kp, Vt, out, B, H, nq, nq_pad, nkv, nkv_pad, dh, c, Kb, Vb, b_from, nkv_pad_b, st);
-        else if (dh == 64) launch_attn<DT, 4, 2, 1>(Qp, Kp, Vt, out, B, H, nq, nq_pad, nkv, nkv_pad, dh, c, Kb, Vb, b_from, nkv_pad_b, st);
-        else if (dh == 32) launch_attn<DT, 2, 1, 1>(Qp, Kp, Vt, out, B, H, nq, nq_pad, nkv, nkv_pad, dh, c, Kb, Vb, b_from, nkv_pad_b, st);
+        if (dh == 72) launch_attn<DT, 5, 3, 0>(Qp, Kp, Vt, out, B, H, nq, nq_pad, nkv, nkv_pad, dh, c, Kb, Vb, b_from, nkv_pad_b, ks, st);
+        else if (dh == 64) launch_attn<DT, 4, 2, 1>(Qp, Kp, Vt, out, B, H, nq, nq_pad, nkv, nkv_pad, dh, c, Kb, Vb, b_from, nkv_pad_b, ks, st);
+        else if (dh == 32) launch_attn<DT, 2, 1, 1>(Qp, Kp, Vt, out, B, H, nq, nq_pad, nkv, nkv_pad, dh, c, Kb, Vb, b_from, nkv_pad_b, ks, st);
         else {
             primx_set_error("primx_attention: unsupported head dim %d (supported: 32, 64, 72)", dh);
             return PRIMX_EINVAL;

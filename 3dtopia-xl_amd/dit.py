@@ -172,7 +172,10 @@ class DiT(nn.Module):
         # forward_with_cfg: the unconditional half's conditioning is ONE embedding expanded to L tokens (dit_crossattn.py:207), so
         # its L rows of to_k / to_v are identical: project 64 + L % 64 of them once per forward and let the cross-attention kernel
         # address them as the L-key sequence (ops.attention(bcast=)) - same tiles, same arithmetic.  PRIMX_NULL_KV_DEDUP=0: the
-        # expanded rows are projected, stored and read like the conditional ones.
+        # expanded rows are projected, stored and read like the conditional ones.  (Both forms give the same bits wherever the
+        # attention launch takes the same form of the kernel.  At batch 1 and N = 2048 it does not: the expanded form holds two
+        # entries with keys of their own and runs the unsplit kernel, the default route splits the keys inside the workgroup
+        # (csrc/attention.hip, KSPLIT) - the two differ at rounding level, inside the same contract.)
         self.dedup_null_kv = os.environ.get("PRIMX_NULL_KV_DEDUP", "1") != "0"
         # weight prefetch of the loader-wave GEMMs (_forward16): 2 = carried by the GEMM launches one or two ahead, 1 = carried by the
         # LayerNorm launches, 0 = off (PRIMX_WPREFETCH)

@@ -546,6 +546,15 @@ def bcast_keys(nkv: int) -> int:
     return 64 + (nkv % 64 if nkv > 64 else 0)
 
 
+def _attn_kernel_name(dtype: torch.dtype, dh: int, b_from: int, H: int, nq_pad: int, nkv: int) -> str:
+    """The name rocprofv3 prints for the 8-wave kernel's launch: its last template argument is the key split, which the library
+    decides (primx_attention_ksplit: the same function the launch asks)."""
+    if PROFILE is None:
+        return "attn_kernel"     # the tag is not recorded
+    tail = f", {_lib.load().primx_attention_ksplit(b_from, H, nq_pad, nkv)}" if _lib.attn_ksplit_available() else ""
+    return f"attn_kernel<{dtype_code(dtype)}, {padded_head_dim(dh) // 16}, {(dh + 31) // 32}, {int(padded_head_dim(dh) == dh)}, 0{tail}>"
+
+
 def attention(Qp: torch.Tensor, Kp: Optional[torch.Tensor], Vt: Optional[torch.Tensor], nq: int, nkv: int, dh: int, scale: float,
               out: Optional[torch.Tensor] = None, bcast: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """bcast = (Kb, Vb): the LAST B - Kp.shape[0] batch entries of Qp attend to nkv copies of one key / value row, held once in
@@ -563,7 +572,7 @@ def attention(Qp: torch.Tensor, Kp: Optional[torch.Tensor], Vt: Optional[torch.T
         nkv_pad = Kp.shape[2] if Kp is not None else nkv_pad_b
         if out is None:
             out = torch.empty(B, nq, H * dh, dtype=Qp.dtype, device=Qp.device)
-        name = f"attn_kernel<{dtype_code(Qp.dtype)}, {padded_head_dim(dh) // 16}, {(dh + 31) // 32}, {int(padded_head_dim(dh) == dh)}, 0>"
+        name = _attn_kernel_name(Qp.dtype, dh, b_from, H, nq_pad, nkv)
         _timed(f"{name} {B * H}x{nq}x{nkv}x{dh}", 4.0 * B * H * nq * nkv * dh, lambda: check(_lib.load().primx_attention_bcast(
             _dev(Qp, "Qp"), _dev(Kp, "Kp", Qp.dtype) if Kp is not None else None, _dev(Vt, "Vt", Qp.dtype) if Kp is not None else None,
             _dev(out, "out", Qp.dtype), B, H, nq, nq_pad, nkv, nkv_pad, dh, scale, _dev(Kb, "Kb", Qp.dtype), _dev(Vb, "Vb", Qp.dtype),
@@ -576,8 +585,7 @@ def attention(Qp: torch.Tensor, Kp: Optional[torch.Tensor], Vt: Optional[torch.T
         out = torch.empty(B, nq, H * dh, dtype=Qp.dtype, device=Qp.device)
     # algorithmic FLOPs: QK^T + PV on the unpadded head dim, softmax excluded
     small = dh == 32 and nq <= 64 and nkv <= 64 and nq_pad == 64 and nkv_pad == 64    # csrc/attention.hip: one wave per problem
-    name = f"attn64_kernel<{dtype_code(Qp.dtype)}>" if small else \
-        f"attn_kernel<{dtype_code(Qp.dtype)}, {padded_head_dim(dh) // 16}, {(dh + 31) // 32}, {int(padded_head_dim(dh) == dh)}, 0>"
+    name = f"attn64_kernel<{dtype_code(Qp.dtype)}>" if small else _attn_kernel_name(Qp.dtype, dh, B, H, nq_pad, nkv)
     _timed(f"{name} {B * H}x{nq}x{nkv}x{dh}", 4.0 * B * H * nq * nkv * dh, lambda: check(_lib.load().primx_attention(
         _dev(Qp, "Qp"), _dev(Kp, "Kp", Qp.dtype), _dev(Vt, "Vt", Qp.dtype), _dev(out, "out", Qp.dtype), B, H, nq,
         nq_pad, nkv, nkv_pad, dh, scale, dtype_code(Qp.dtype), _stream()), "primx_attention"))

@@ -351,6 +351,17 @@ int primx_attention(const void* Qp, const void* Kp, const void* Vt, void* out, i
 int primx_attention_bcast(const void* Qp, const void* Kp, const void* Vt, void* out, int B, int H, int nq, int nq_pad, int nkv,
                           int nkv_pad, int dh, float scale, const void* Kb, const void* Vb, int b_from, int nkv_pad_b, int dtype,
                           void* stream);
+/* The key split of primx_attention[_bcast] (csrc/attention.hip, KSPLIT): a launch whose 256-row workgroups would cover at most
+ * half of the device's CUs runs 128-row workgroups whose two wave groups each walk half of the key tiles, merged in LDS.  It is
+ * taken iff  ceil(nkv / 64) >= 16  and  2 * b_from * H * ceil(nq_pad / 256) <= CUs  (b_from = the entries with keys of their own,
+ * B for primx_attention: the decision does not depend on broadcast entries riding along).  A split launch differs from the unsplit
+ * one at rounding level (a few more fp32 roundings in O), inside the same contract.  Added to ABI 35 without a new number: no
+ * existing call changes.
+ * primx_attention_ksplit_mode: -1 = the rule (default; PRIMX_ATTN_KSPLIT=0 in the environment starts with 0), 0 = never,
+ * 1 = whenever ceil(nkv / 64) >= 16; returns the mode it replaces.  primx_attention_ksplit: what the current mode decides for a
+ * launch (0 / 1). */
+int primx_attention_ksplit_mode(int mode);
+int primx_attention_ksplit(int b_from, int H, int nq_pad, int nkv);
 
 /* ----------------------------------------------------------------------------------------------
  * The DiT blocks of one planned, folded forward from ONE call (ABI 24)
