@@ -81,6 +81,7 @@ SIGNATURES = {
     "primx_attention_bcast": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _i, _i, _i, _p],
     "primx_attention_ksplit_mode": [_i],
     "primx_attention_ksplit": [_i, _i, _i, _i],
+    "primx_gemm_toq64_mode": [_i],
     "primx_pack_heads": [_p, _l, _l, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "primx_cfg_combine": [_p, _p, _i, _l, _f, _p],
     "primx_diffusion_step": [_p, _p, _i, _l, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p],
@@ -168,7 +169,8 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # primx_material_sample (_MATERIAL_ENTRY_POINTS) was added to version 35 without a new number, because it changes no existing call: an
 # A/B build of version 35 from before it lacks the symbol and serves everything but a MeshField with a material;
 # the attention key split's switch and query (_ATTN_KSPLIT_ENTRY_POINTS) joined version 35 the same way: a build from before them
-# never splits (`attn_ksplit_available()`)
+# never splits (`attn_ksplit_available()`); the switch of to_q's 64-row tile under the null skip (_TOQ64_ENTRY_POINTS) likewise: a build
+# from before it runs that launch on the 128-row tile (`toq64_available()`)
 _FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
                            "primx_linear_fold"}
 _MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
@@ -187,6 +189,7 @@ _REFINE_ENTRY_POINTS: set = {"primx_primsdf_query_backward", "primx_adam_step"}
 _RAYMARCH_GRAD_ENTRY_POINTS: set = {"primx_raymarch_backward"}
 _MATERIAL_ENTRY_POINTS: set = {"primx_material_sample"}
 _ATTN_KSPLIT_ENTRY_POINTS: set = {"primx_attention_ksplit_mode", "primx_attention_ksplit"}
+_TOQ64_ENTRY_POINTS: set = {"primx_gemm_toq64_mode"}
 _AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34)
 _fold_available: dict = {}
 _blocks_call: dict = {}
@@ -194,6 +197,7 @@ _kv_ride: dict = {}
 _f32out_group: dict = {}
 _null_skip: dict = {}
 _attn_ksplit: dict = {}
+_toq64: dict = {}
 
 _lib: Optional[C.CDLL] = None
 
@@ -261,7 +265,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
             continue
         if got < 35 and name in _RAYMARCH_GRAD_ENTRY_POINTS:
             continue
-        if ab and (name in _MATERIAL_ENTRY_POINTS or name in _ATTN_KSPLIT_ENTRY_POINTS or name == "primx_dit_blocks_fold_features") and not hasattr(lib, name):
+        if ab and (name in _MATERIAL_ENTRY_POINTS or name in _ATTN_KSPLIT_ENTRY_POINTS or name in _TOQ64_ENTRY_POINTS
+                   or name == "primx_dit_blocks_fold_features") and not hasattr(lib, name):
             continue                # an A/B build from before the entry point existed (same version number)
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
@@ -272,6 +277,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     _f32out_group[path] = got >= 26
     _null_skip[path] = got >= 35 and hasattr(lib, "primx_dit_blocks_fold_features") and bool(lib.primx_dit_blocks_fold_features() & 1)
     _attn_ksplit[path] = hasattr(lib, "primx_attention_ksplit")
+    _toq64[path] = hasattr(lib, "primx_gemm_toq64_mode")
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -312,6 +318,12 @@ def attn_ksplit_available() -> bool:
     """Does the loaded library carry the attention key split and its switch?  (False only for an older PRIMX_LIB A/B build.)"""
     load()
     return _attn_ksplit.get(LIB_PATH, False)
+
+
+def toq64_available() -> bool:
+    """Does the loaded library carry the 64-row tile of to_q under the null skip and its switch?  (False only for an older PRIMX_LIB A/B build.)"""
+    load()
+    return _toq64.get(LIB_PATH, False)
 
 
 def check(status: int, name: str) -> None:

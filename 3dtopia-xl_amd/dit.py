@@ -163,6 +163,9 @@ class DiT(nn.Module):
         # accumulation leaves it.  The LayerNorm fold, the one-call route and the K / V riders carry it (include/primx_hip.h,
         # PrimxDitForwardFold::null_vrow).  Not with `cfg_streams` (each half is a chain of its own there).
         self.null_xattn_skip = os.environ.get("PRIMX_NULL_XATTN_SKIP", "1") != "0"
+        # `null_kv_once` (default on): a forward that skips reads nothing of the broadcast K / V entry once its conditioning state
+        # holds the value rows, so it does not project that entry again (_forward16, `reads_null`); False projects it in every forward
+        self.null_kv_once = True
         # `collapse_null_cross_attention`: the opt-in from before the skip (round 3) - the same shortcut without `dedup_null_kv`
         # and without the -0 rule ("exact algebra up to rounding"); unfolded forwards only, a folded forward ignores it.
         self.collapse_null_cross_attention = False
@@ -748,14 +751,26 @@ class DiT(nn.Module):
             wkv, bkv = pk["w_kv_all"][i * 2 * D:(i + 1) * 2 * D], pk["b_kv_all"][i * 2 * D:(i + 1) * 2 * D]
             return (y16[:Bkv * Lk], wkv, bkv, Lk, H, dh, [HEADS_KROWS, HEADS_VT], [Kc_blk[i], Vc_blk[i]], Kc.shape[2], 1.0, Bkv * L)
 
-        def project_kv(cond_rows: bool) -> None:
-            # (cond_rows False: the one-call route projects the conditional entries itself - `kv_ride`)
+        # `null_kv_once`: who last projected the broadcast entry is written ON the buffers (the token of the conditioning state): a new
+        # buffer from _heads carries no token, a buffer shared with another conditioning state (the key of Kn / Vn does not depend on
+        # the batch size) carries that one's, and repack() drops the buffers and the state alike - each reads as "not valid"
+        def null_kv_valid() -> bool:
+            tok = cs.get("null_tok")
+            return tok is not None and getattr(Kn, "_primx_null_tok", None) is tok and getattr(Vn, "_primx_null_tok", None) is tok
+
+        def project_null_kv() -> None:
+            ops.linear_heads(cs["null16"], pk["w_kv_all"], pk["b_kv_all"], Ln, H, dh, [HEADS_KROWS, HEADS_VT], [Kn, Vn],
+                             Kn.shape[2], n_rep=self.depth, rep_batches=1)
+            Kn._primx_null_tok = Vn._primx_null_tok = cs.setdefault("null_tok", object())
+
+        def project_kv(cond_rows: bool, null_rows: bool) -> None:
+            # (cond_rows False: the one-call route projects the conditional entries itself - `kv_ride`; null_rows False: nothing of
+            # this forward reads the broadcast entry)
             if cond_rows:
                 ops.linear_heads(y16[:Bkv * Lk], pk["w_kv_all"], pk["b_kv_all"], Lk, H, dh, [HEADS_KROWS, HEADS_VT], [Kc, Vc],
                                  Kc.shape[2], n_rep=self.depth, rep_batches=Bkv, real_rows=Bkv * L)
-            if dedup:
-                ops.linear_heads(cs["null16"], pk["w_kv_all"], pk["b_kv_all"], Ln, H, dh, [HEADS_KROWS, HEADS_VT], [Kn, Vn],
-                                 Kn.shape[2], n_rep=self.depth, rep_batches=1)
+            if null_rows:
+                project_null_kv()
             cs["kv_valid"], cs["kv_id"] = True, (Kc.data_ptr(), Vc.data_ptr())
         Qs = self._heads("Qs", Be, N, HEADS_ROWS, dt, dev, ops.BQ)
         Ks = self._heads("Ks", Be, N, HEADS_KROWS, dt, dev, ops.BQ)
@@ -972,14 +987,22 @@ class DiT(nn.Module):
         ride = (need_kv and self.kv_ride and fold_uv is not None and not two_streams and _lib.kv_ride_available()
                 and ops.fold_pair_fits(T, N, D, H, Bkv * Lk, Lk, Dc))
         ride_state["on"] = ride and not one_call
+        # The broadcast entry Kn / Vn depends on the null embedding and the packed weights only.  Its readers: the broadcast attention
+        # and the value-row gather of a forward that does not skip, and null_value_rows() below.  A forward that skips and finds the
+        # value rows of its conditioning state reads nothing of it and does not project it (`null_kv_once`; one 44 us launch per forward
+        # at DiT-XL); a forward that reads it projects it as before, and where the conditional projection is reused (`reuse_cond_kv`)
+        # it projects the entry unless this conditioning state was the last to do so.
+        reads_null = dedup and not (self.null_kv_once and skip and cs.get("vrow") is not None)
         if need_kv:
-            project_kv(not ride)
+            project_kv(not ride, reads_null)
             if ride_state["on"]:
                 ops.linear_heads_fold_pair(None, *kv_problem(0))     # block 0's projection: a launch of its own, on the riders' tile kernel
+        elif reads_null and not null_kv_valid():
+            project_null_kv()
         if skip and cs.get("vrow") is None:
             # ONCE per conditioning state, behind the broadcast entry's first projection: the rows depend on the null embedding and
             # the packed to_v weights only, which live exactly as long as `cs` does (`null16` above; repack() drops both) - every
-            # later forward of the loop re-projects the same bits into Vn and launches nothing here
+            # later forward of the loop launches nothing here (and, with `null_kv_once`, does not project the entry either)
             cs["vrow"] = null_value_rows()
         if two_streams:
             # Two HIP streams, one per CFG half (the conditional and the unconditional rows are independent chains of

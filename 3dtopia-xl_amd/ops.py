@@ -442,6 +442,14 @@ def linear_heads_fold(A: torch.Tensor, W: torch.Tensor, rows_per_batch: int, hea
         fa[0], fa[1], fa[2], fa[3], fa[4], eps, dtype_code(A.dtype), cp, cn, _stream()), "primx_linear_heads_fold"))
 
 
+def gemm_toq64_mode(mode: int) -> int:
+    """The switch of to_q's 64-row tile under the null cross-attention skip (primx_gemm_toq64_mode, include/primx_hip.h): 1 = the rule
+    (default), 0 = never (the 128-row tile).  Returns the mode it replaces; same bits either way."""
+    if not _lib.toq64_available():
+        raise RuntimeError("the loaded library has no 64-row to_q tile (an older PRIMX_LIB build)")
+    return int(_lib.load().primx_gemm_toq64_mode(int(mode)))
+
+
 def fold_pair_fits(T: int, rows_per_batch: int, D: int, heads: int, kv_rows: int, kv_rows_per_batch: int, kv_K: int) -> bool:
     """Will primx_linear_heads_fold_pair run a DiT block's qkv projection (T token rows) and the next block's to_k / to_v projection
     (kv_rows conditioning rows) as ONE launch?  The rule of csrc/gemm.hip: both on the 256 x 288 heads tile, the first problem one

@@ -363,6 +363,14 @@ int primx_attention_bcast(const void* Qp, const void* Kp, const void* Vt, void* 
 int primx_attention_ksplit_mode(int mode);
 int primx_attention_ksplit(int b_from, int H, int nq_pad, int nkv);
 
+/* The 64-row tile of the heads-fold consumer (csrc/gemm.hip, gemm144l64_dma_kernel): to_q under the null cross-attention skip - the
+ * launch of primx_dit_blocks_fold that multiplies the attending entries' rows only and finishes the other rows' statistics - runs on
+ * 64 x 144 tiles iff the 256 x 288 tile is not taken,  M % 64 == 0  and  2 * ceil(M / 128) * (N / 144) <= CUs  (the 128-row tiles
+ * would leave at least half of the CUs without a workgroup).  Same MFMA chain per element, same bits as the 128-row tile.  No other
+ * launch takes it.  Added to ABI 35 without a new number: no existing call changes.
+ * primx_gemm_toq64_mode: 1 = the rule (default), 0 = never; returns the mode it replaces. */
+int primx_gemm_toq64_mode(int mode);
+
 /* ----------------------------------------------------------------------------------------------
  * The DiT blocks of one planned, folded forward from ONE call (ABI 24)
  * -------------------------------------------------------------------------------------------- */
