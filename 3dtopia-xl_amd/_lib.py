@@ -148,56 +148,45 @@ SIGNATURES = {
     "primx_material_sample": [_p, _p, _p, _l, _p, _i, _p, _p, _i, _p, _i, _p, _l, _p, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
-# an alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI: version 21 changed the
-# argument lists of the GEMM / LayerNorm entry points (explicit prefetch ranges), so older libraries cannot be bound any more;
-# versions 22 / 23 only added / re-typed the LayerNorm-fold entry points, so a version-21 or -22 build can stand in as long as
-# nothing folds: the fold prototypes are not bound to such a build and `fold_available()` is False (ops.fold_shapes_ok asks);
-# version 24 added primx_dit_blocks_fold (one foreign call for a forward's blocks): a version-23 build lacks only that one, and the
-# host then issues the launches itself (`blocks_call_available()`); version 25 added primx_linear_heads_fold_pair and the kv_* tail of
-# PrimxDitForwardFold (a version-24 build ignores the tail: the host then projects K / V itself, `kv_ride_available()`); version 26 added
-# primx_linear_f32out_group (`f32out_group_available()`: without it the fold's u / v rows are one launch per site); version 27
-# added the mesh-extraction entry points (_MESH_ENTRY_POINTS: a version-26 build serves everything but mesh.py); version 28 added
-# the texture-bake entry points (_TEXBAKE_ENTRY_POINTS: a version-27 build serves everything but mesh.py's texture bake); version
-# 29 added the mesh-cleanup entry points (_MESHCLEAN_ENTRY_POINTS: a version-28 build serves everything but mesh.clean_mesh);
-# version 30 added the mesh-decimation entry points (_MESHDECIM_ENTRY_POINTS: a version-29 build serves everything but
-# mesh.decimate_mesh); version 31 added the VAE encoder's entry points (_VAEENC_ENTRY_POINTS: a version-30 build serves everything
-# but VAE.encode / VAE.forward and pipeline.primitives_to_latents); version 32 added the editing entry points (_EDIT_ENTRY_POINTS:
-# a version-31 build serves everything but q_sample, ddim_reverse_sample and the kept-token DDIM loops); version 33 added the
-# primitive-fitting entry points (_FIT_ENTRY_POINTS: a version-32 build serves everything but fit.py); version 34 added the
-# refinement entry points (_REFINE_ENTRY_POINTS: a version-33 build serves everything but the differentiable PrimSDF and refine=);
-# version 35 added primx_raymarch_backward (_RAYMARCH_GRAD_ENTRY_POINTS: a version-34 build serves everything but the marcher's backward);
-# primx_material_sample (_MATERIAL_ENTRY_POINTS) was added to version 35 without a new number, because it changes no existing call: an
-# A/B build of version 35 from before it lacks the symbol and serves everything but a MeshField with a material;
-# the attention key split's switch and query (_ATTN_KSPLIT_ENTRY_POINTS) joined version 35 the same way: a build from before them
-# never splits (`attn_ksplit_available()`); the switch of to_q's 64-row tile under the null skip (_TOQ64_ENTRY_POINTS) likewise: a build
-# from before it runs that launch on the 128-row tile (`toq64_available()`)
-_FOLD_ENTRY_POINTS: set = {"primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
-                           "primx_linear_fold"}
-_MESH_ENTRY_POINTS: set = {"primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"}
-_TEXBAKE_ENTRY_POINTS: set = {"primx_texbake_labels", "primx_texbake_components_workspace", "primx_texbake_components",
-                              "primx_texbake_raster_workspace", "primx_texbake_raster", "primx_texbake_compact",
-                              "primx_texbake_fill_workspace", "primx_texbake_fill"}
-_MESHCLEAN_ENTRY_POINTS: set = {"primx_meshclean_workspace", "primx_meshclean_merge", "primx_meshclean_faces",
-                                "primx_meshclean_components", "primx_meshclean_edges", "primx_meshclean_fans"}
-_MESHDECIM_ENTRY_POINTS: set = {"primx_meshdecim_workspace", "primx_meshdecim_edges", "primx_meshdecim_quadrics",
-                                "primx_meshdecim_costs", "primx_meshdecim_select", "primx_meshdecim_collapse",
-                                "primx_meshdecim_finish", "primx_meshdecim_normals"}
-_VAEENC_ENTRY_POINTS: set = {"primx_latent_norm", "primx_enc_conv_in", "primx_conv3d_down_s8c32", "primx_enc_head"}
-_EDIT_ENTRY_POINTS: set = {"primx_q_sample", "primx_diffusion_reverse_step", "primx_diffusion_step_keep"}
-_FIT_ENTRY_POINTS: set = {"primx_mesh_field_query", "primx_mesh_face_areas", "primx_mesh_surface_points", "primx_fps"}
-_REFINE_ENTRY_POINTS: set = {"primx_primsdf_query_backward", "primx_adam_step"}
-_RAYMARCH_GRAD_ENTRY_POINTS: set = {"primx_raymarch_backward"}
-_MATERIAL_ENTRY_POINTS: set = {"primx_material_sample"}
-_ATTN_KSPLIT_ENTRY_POINTS: set = {"primx_attention_ksplit_mode", "primx_attention_ksplit"}
-_TOQ64_ENTRY_POINTS: set = {"primx_gemm_toq64_mode"}
+# An alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI.  Version 21 changed the argument
+# lists of the GEMM / LayerNorm entry points (explicit prefetch ranges), so older libraries cannot be bound any more; every later
+# version only ADDED entry points (23 also re-typed the fold's: an older build's are not bound), so an older build serves everything
+# but what it lacks.  _SINCE: entry point -> the first ABI version that has it (not listed: 21).  _PROBE marks those that joined
+# version 35 without a new number, because they change no existing call: an A/B build of version 35 from before them lacks the
+# symbol, which `load` finds out with hasattr.  A version-24 build ignores the kv_* tail of PrimxDitForwardFold that came with
+# primx_linear_heads_fold_pair (the host then projects K / V itself).
+_PROBE = 0
+_SINCE: dict = {
+    **dict.fromkeys(("primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
+                     "primx_linear_fold"), 23),                                                  # the LayerNorm fold
+    "primx_dit_blocks_fold": 24,                                                                 # one foreign call for a forward's blocks
+    "primx_linear_heads_fold_pair": 25,                                                          # the K / V riders
+    "primx_linear_f32out_group": 26,                                                             # the fold's u / v rows in one launch
+    **dict.fromkeys(("primx_mcubes_workspace", "primx_mcubes_count", "primx_mcubes_emit", "primx_noise_filter"), 27),   # mesh.py
+    **dict.fromkeys(("primx_texbake_labels", "primx_texbake_components_workspace", "primx_texbake_components",
+                     "primx_texbake_raster_workspace", "primx_texbake_raster", "primx_texbake_compact",
+                     "primx_texbake_fill_workspace", "primx_texbake_fill"), 28),                 # mesh.py's texture bake
+    **dict.fromkeys(("primx_meshclean_workspace", "primx_meshclean_merge", "primx_meshclean_faces", "primx_meshclean_components",
+                     "primx_meshclean_edges", "primx_meshclean_fans"), 29),                      # mesh.clean_mesh
+    **dict.fromkeys(("primx_meshdecim_workspace", "primx_meshdecim_edges", "primx_meshdecim_quadrics", "primx_meshdecim_costs",
+                     "primx_meshdecim_select", "primx_meshdecim_collapse", "primx_meshdecim_finish",
+                     "primx_meshdecim_normals"), 30),                                            # mesh.decimate_mesh
+    **dict.fromkeys(("primx_latent_norm", "primx_enc_conv_in", "primx_conv3d_down_s8c32", "primx_enc_head"), 31),   # VAE.encode
+    **dict.fromkeys(("primx_q_sample", "primx_diffusion_reverse_step", "primx_diffusion_step_keep"), 32),             # editing
+    **dict.fromkeys(("primx_mesh_field_query", "primx_mesh_face_areas", "primx_mesh_surface_points", "primx_fps"), 33),  # fit.py
+    **dict.fromkeys(("primx_primsdf_query_backward", "primx_adam_step"), 34),                    # differentiable PrimSDF, refine=
+    "primx_raymarch_backward": 35,                                                               # the marcher's backward
+    **dict.fromkeys(("primx_material_sample",                                                    # a MeshField with a material
+                     "primx_attention_ksplit_mode", "primx_attention_ksplit",                    # without them: attention never splits its keys
+                     "primx_gemm_toq64_mode",                                                    # without it: to_q under the null skip on the 128-row tile
+                     "primx_dit_blocks_fold_features"), _PROBE),                                 # bit 0: the null skip's tail of PrimxDitForwardFold is read
+}
+# what the DiT's route asks of the library (`capabilities`): feature -> the entry point whose presence tells
+_FEATURES: dict = {"fold": "primx_linear_fold", "blocks_call": "primx_dit_blocks_fold", "kv_ride": "primx_linear_heads_fold_pair",
+                   "f32out_group": "primx_linear_f32out_group", "null_skip": "primx_dit_blocks_fold_features",
+                   "attn_ksplit": "primx_attention_ksplit", "toq64": "primx_gemm_toq64_mode"}
 _AB_ABI_VERSIONS: tuple = (21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34)
-_fold_available: dict = {}
-_blocks_call: dict = {}
-_kv_ride: dict = {}
-_f32out_group: dict = {}
-_null_skip: dict = {}
-_attn_ksplit: dict = {}
-_toq64: dict = {}
+_caps: dict = {}        # library path -> frozenset of feature names
 
 _lib: Optional[C.CDLL] = None
 
@@ -238,92 +227,60 @@ def load(path: Optional[str] = None) -> C.CDLL:
     got = lib.primx_abi_version()
     if got != ABI_VERSION and not (ab and got in _AB_ABI_VERSIONS):
         raise RuntimeError(f"libprimx_hip.so ABI {got} != expected {ABI_VERSION}; rebuild it")
+    bound = set()
     for name, argtypes in SIGNATURES.items():
-        if got < 23 and name in _FOLD_ENTRY_POINTS:
-            continue                # an older A/B build: its fold entry points (if any) have other argument lists
-        if got < 24 and name == "primx_dit_blocks_fold":
-            continue
-        if got < 25 and name == "primx_linear_heads_fold_pair":
-            continue
-        if got < 26 and name == "primx_linear_f32out_group":
-            continue
-        if got < 27 and name in _MESH_ENTRY_POINTS:
-            continue
-        if got < 28 and name in _TEXBAKE_ENTRY_POINTS:
-            continue
-        if got < 29 and name in _MESHCLEAN_ENTRY_POINTS:
-            continue
-        if got < 30 and name in _MESHDECIM_ENTRY_POINTS:
-            continue
-        if got < 31 and name in _VAEENC_ENTRY_POINTS:
-            continue
-        if got < 32 and name in _EDIT_ENTRY_POINTS:
-            continue
-        if got < 33 and name in _FIT_ENTRY_POINTS:
-            continue
-        if got < 34 and name in _REFINE_ENTRY_POINTS:
-            continue
-        if got < 35 and name in _RAYMARCH_GRAD_ENTRY_POINTS:
-            continue
-        if ab and (name in _MATERIAL_ENTRY_POINTS or name in _ATTN_KSPLIT_ENTRY_POINTS or name in _TOQ64_ENTRY_POINTS
-                   or name == "primx_dit_blocks_fold_features") and not hasattr(lib, name):
-            continue                # an A/B build from before the entry point existed (same version number)
+        since = _SINCE.get(name, 21)
+        if got < since or (since == _PROBE and ab and not hasattr(lib, name)):
+            continue                # an older A/B build: it lacks the entry point (or, before 23, has it with another argument list)
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, C.c_int)
-    _fold_available[path] = got >= 23
-    _blocks_call[path] = got >= 24
-    _kv_ride[path] = got >= 25
-    _f32out_group[path] = got >= 26
-    _null_skip[path] = got >= 35 and hasattr(lib, "primx_dit_blocks_fold_features") and bool(lib.primx_dit_blocks_fold_features() & 1)
-    _attn_ksplit[path] = hasattr(lib, "primx_attention_ksplit")
-    _toq64[path] = hasattr(lib, "primx_gemm_toq64_mode")
+        bound.add(name)
+    _caps[path] = frozenset(f for f, name in _FEATURES.items() if name in bound
+                            and (f != "null_skip" or (got >= 35 and lib.primx_dit_blocks_fold_features() & 1)))
     if path == LIB_PATH:
         _lib = lib
     return lib
 
 
+def capabilities(path: Optional[str] = None) -> frozenset:
+    """What the library at `path` (default: the loaded one) can do, as feature names: "fold" (the LayerNorm-fold entry points, ABI 23),
+    "blocks_call" (primx_dit_blocks_fold, 24), "kv_ride" (it projects the conditioning K / V itself, on the qkv launches, 25),
+    "f32out_group" (primx_linear_f32out_group, 26), "null_skip" (primx_dit_blocks_fold reads the null cross-attention skip's tail),
+    "attn_ksplit" (the attention key split and its switch), "toq64" (to_q's 64-row tile under the null skip and its switch).  Only an
+    older PRIMX_LIB A/B build lacks any of them."""
+    path = path or LIB_PATH
+    if path not in _caps:
+        load(path)
+    return _caps[path]
+
+
 def fold_available() -> bool:
-    """Does the loaded library carry the LayerNorm-fold entry points of this ABI?  (False only for an older PRIMX_LIB A/B build.)"""
-    load()
-    return _fold_available.get(LIB_PATH, False)
+    return "fold" in capabilities()
 
 
 def blocks_call_available() -> bool:
-    """Does the loaded library carry primx_dit_blocks_fold (ABI 24)?"""
-    load()
-    return _blocks_call.get(LIB_PATH, False)
+    return "blocks_call" in capabilities()
 
 
 def kv_ride_available() -> bool:
-    """Does the loaded library's primx_dit_blocks_fold project the conditioning K / V itself (ABI 25: riders on the qkv launches)?"""
-    load()
-    return _kv_ride.get(LIB_PATH, False)
+    return "kv_ride" in capabilities()
 
 
 def f32out_group_available() -> bool:
-    """Does the loaded library carry primx_linear_f32out_group (ABI 26)?"""
-    load()
-    return _f32out_group.get(LIB_PATH, False)
+    return "f32out_group" in capabilities()
 
 
 def null_skip_available() -> bool:
-    """Does the loaded library's primx_dit_blocks_fold read the null cross-attention skip's tail of PrimxDitForwardFold?  (False only
-    for a PRIMX_LIB A/B build from before it; same version number, told apart by primx_dit_blocks_fold_features.)"""
-    load()
-    return _null_skip.get(LIB_PATH, False)
+    return "null_skip" in capabilities()
 
 
 def attn_ksplit_available() -> bool:
-    """Does the loaded library carry the attention key split and its switch?  (False only for an older PRIMX_LIB A/B build.)"""
-    load()
-    return _attn_ksplit.get(LIB_PATH, False)
+    return "attn_ksplit" in capabilities()
 
 
 def toq64_available() -> bool:
-    """Does the loaded library carry the 64-row tile of to_q under the null skip and its switch?  (False only for an older PRIMX_LIB A/B build.)"""
-    load()
-    return _toq64.get(LIB_PATH, False)
+    return "toq64" in capabilities()
 
 
 def check(status: int, name: str) -> None:

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from typing import Dict, Optional
 
 import torch
@@ -84,7 +85,7 @@ class Mlp(nn.Module):
 
 class DiTBlock(nn.Module):
     """adaLN-Zero block: cross-attn, self-attn, MLP, each gated (models/dit_crossattn.py:25-58).
-    Parameter container; the fused per-block schedule lives in ``DiT._run_block``."""
+    Parameter container; the fused per-block schedule lives in ``_Forward16.block``."""
 
     def __init__(self, hidden_size, cross_attn_cond_dim, num_heads, mlp_ratio=4.0, proj_bias=False,
                  gradient_checkpointing=False, **block_kwargs):
@@ -106,6 +107,271 @@ class FinalLayer(nn.Module):
         super().__init__()
         self.linear = nn.Linear(hidden_size, out_channels, bias=True)
         self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 2 * hidden_size, bias=True))
+
+
+# What one 16-bit forward does: decided once, field by field, in DiT._route16; DiT._forward16 and _Forward16 only read it.
+_Route16 = namedtuple("_Route16", "dedup Bkv two_streams fuse ln_tail fold skip collapse one_call need_kv ride ride_in_python reads_null wpf")
+
+
+class _Forward16:
+    """One 16-bit forward's operands and the launches over them; built by DiT._forward16 (model `m`) once the route `r` is known."""
+
+    def __init__(self, m: "DiT", r: _Route16, pk: Dict, cs: Dict, plan: Optional[Dict], h, mod, B: int, N: int, L: int, dt):
+        dev, D, H, depth, Be, Lk = h.device, m.hidden_size, m.num_heads, m.depth, mod.shape[0], cs["Lk"]
+        self.m, self.r, self.pk, self.cs, self.plan, self.h, self.mod, self.dt = m, r, pk, cs, plan, h, mod, dt
+        self.B, self.Be, self.N, self.L, self.Lk, self.D, self.H, self.dh, self.T = B, Be, N, L, Lk, D, H, D // H, Be * N
+        self.blocks, self.y16, self.scale = pk["blocks"], cs["y16"], (D // H) ** -0.5
+        self.prow, self.nq_pad = plan["row"] if plan is not None else None, ops.round_up(N, ops.BQ)
+        self.Qc = m._heads("Qc", Be, N, HEADS_ROWS, dt, dev, ops.BQ)
+        Kc, Vc = self.Kc, self.Vc = m._kv_operands(r.Bkv, L, Lk, dt, dev)
+        self.Kc_blk, self.Vc_blk = Kc.view(depth, r.Bkv, *Kc.shape[1:]), Vc.view(depth, r.Bkv, *Vc.shape[1:])
+        self.Kn_blk = self.Vn_blk = self.sync = self.fold_uv = self.fcent = self.fpart = None
+        if r.dedup:
+            self.Ln = ops.bcast_keys(L)
+            Kn, Vn = self.Kn, self.Vn = [m._heads(tag, depth, self.Ln, kind, dt, dev, ops.BKV) for tag, kind in (("Kn", HEADS_KROWS), ("Vn", HEADS_VT))]
+            self.Kn_blk, self.Vn_blk = Kn.view(depth, 1, *Kn.shape[1:]), Vn.view(depth, 1, *Vn.shape[1:])
+        self.Qs, self.Ks, self.Vs = (m._heads(tag, Be, N, kind, dt, dev, ops.BQ)
+                                     for tag, kind in (("Qs", HEADS_ROWS), ("Ks", HEADS_KROWS), ("Vs", HEADS_VT)))
+        self.xn, self.att = torch.empty(self.T, D, dtype=dt, device=dev), torch.empty(Be, N, D, dtype=dt, device=dev)
+        self.hid = torch.empty(self.T, pk["blocks"][0]["w_fc1"].shape[0], dtype=dt, device=dev) if depth else None
+        if r.ln_tail:
+            # (two regions: with `cfg_streams` the two halves run concurrently and must not share words)
+            self.sync_w, self.sync = ops.ln_sync_words(self.T), m._ln_sync.get(str(dev))
+            if self.sync is None or self.sync.numel() < 2 * self.sync_w:
+                self.sync = m._ln_sync[str(dev)] = torch.zeros(2 * self.sync_w, dtype=torch.int32, device=dev)
+        base = depth * 9 * D
+        self.fin_mod = (mod[:, base:base + D], mod[:, base + D:base + 2 * D])    # final layer's shift / scale
+        if r.fold:
+            self.fold_uv = m._fold_tables(plan, dt, pk)["uv"]
+            if dt == torch.float16:
+                m._fold_fp16_used = True
+            wk = (str(dev), self.T)
+            if wk not in m._fold_ws:
+                m._fold_ws = {wk: ops.fold_workspace(self.T, D, dev)}
+            self.fcent, self.fpart = m._fold_ws[wk]
+        self.fside: Dict[int, int] = {}                  # per row range (its b0): which of the fold's two (centre, scale) arrays the current site reads
+
+    def null_value_rows(self) -> torch.Tensor:
+        # [depth, D] 16-bit: per block the value row of the H heads side by side, out of the broadcast entry's V^T layout [1, H, DP,
+        # n_pad] (key 0 sits at position 0 of its quad-permuted group), -0 -> +0 on the bit pattern (0x8000 in both 16-bit types)
+        depth, Vn = self.m.depth, self.Vn
+        bits = Vn.view(depth, self.H, Vn.shape[2], Vn.shape[3])[:, :, :self.dh, 0].view(torch.int16)
+        return torch.where(bits == -32768, 0, bits).reshape(depth, self.D).contiguous().view(self.dt)
+
+    def kv_problem(self, i: int):
+        # block i's [to_k; to_v] projection of the conditional entries as the heads GEMM primx_linear_heads_fold_pair carries
+        D, Bkv, pk = self.D, self.r.Bkv, self.pk
+        wkv, bkv = pk["w_kv_all"][i * 2 * D:(i + 1) * 2 * D], pk["b_kv_all"][i * 2 * D:(i + 1) * 2 * D]
+        return (self.y16[:Bkv * self.Lk], wkv, bkv, self.Lk, self.H, self.dh, [HEADS_KROWS, HEADS_VT], [self.Kc_blk[i], self.Vc_blk[i]],
+                self.Kc.shape[2], 1.0, Bkv * self.L)
+
+    # `null_kv_once`: who last projected the broadcast entry is written ON the buffers (the token of the conditioning state): a new
+    # buffer from _heads carries no token, a buffer shared with another conditioning state (the key of Kn / Vn does not depend on
+    # the batch size) carries that one's, and repack() drops the buffers and the state alike - each reads as "not valid"
+    def null_kv_valid(self) -> bool:
+        tok = self.cs.get("null_tok")
+        return tok is not None and getattr(self.Kn, "_primx_null_tok", None) is tok and getattr(self.Vn, "_primx_null_tok", None) is tok
+
+    def project_null_kv(self) -> None:
+        ops.linear_heads(self.cs["null16"], self.pk["w_kv_all"], self.pk["b_kv_all"], self.Ln, self.H, self.dh, [HEADS_KROWS, HEADS_VT],
+                         [self.Kn, self.Vn], self.Kn.shape[2], n_rep=self.m.depth, rep_batches=1)
+        self.Kn._primx_null_tok = self.Vn._primx_null_tok = self.cs.setdefault("null_tok", object())
+
+    def project_kv(self) -> None:
+        r, cs, pk, Kc, Vc, Bkv = self.r, self.cs, self.pk, self.Kc, self.Vc, self.r.Bkv
+        if r.need_kv:
+            if not r.ride:                               # (`kv_ride`: the riders project the conditional entries, block by block)
+                ops.linear_heads(self.y16[:Bkv * self.Lk], pk["w_kv_all"], pk["b_kv_all"], self.Lk, self.H, self.dh, [HEADS_KROWS, HEADS_VT],
+                                 [Kc, Vc], Kc.shape[2], n_rep=self.m.depth, rep_batches=Bkv, real_rows=Bkv * self.L)
+            if r.reads_null:                             # (else nothing of this forward reads the broadcast entry)
+                self.project_null_kv()
+            cs["kv_valid"], cs["kv_id"] = True, (Kc.data_ptr(), Vc.data_ptr())
+            if r.ride_in_python:
+                ops.linear_heads_fold_pair(None, *self.kv_problem(0))     # block 0's projection: a launch of its own, on the riders' tile kernel
+        elif r.reads_null and not self.null_kv_valid():
+            self.project_null_kv()
+        if r.skip and cs.get("vrow") is None:
+            # ONCE per conditioning state, behind the broadcast entry's first projection: the rows depend on the null embedding and
+            # the packed to_v weights only, which live exactly as long as `cs` does (`null16`; repack() drops both) - every
+            # later forward of the loop launches nothing here (and, with `null_kv_once`, does not project the entry either)
+            cs["vrow"] = self.null_value_rows()
+
+    def fold_call(self, with_kv: bool):
+        # the arguments of primx_dit_blocks_fold: this forward's struct and the per-block descriptors (built once per planned loop)
+        m, r, pk, blocks, fold_uv, Kc, hid = self.m, self.r, self.pk, self.blocks, self.fold_uv, self.Kc, self.hid
+        dedup, wpf, Bkv, fd = r.dedup, r.wpf, r.Bkv, self.plan["fold"]
+        dkey = (Kc.data_ptr(), self.Vc.data_ptr(), self.Kn_blk[0].data_ptr() if dedup else 0, wpf, Bkv)
+        if fd.get("desc_key") != dkey:
+            arr = (_lib.DitBlockFold * m.depth)()
+            for i, w in enumerate(blocks):
+                d = arr[i]
+                for name in ("w_q", "b_q", "w_cproj", "b_cproj", "w_qkv", "w_proj", "b_proj", "w_fc1", "w_fc2", "b_fc2"):
+                    setattr(d, name, None if w[name] is None else w[name].data_ptr())
+                d.Kc, d.Vc = self.Kc_blk[i].data_ptr(), self.Vc_blk[i].data_ptr()
+                d.Kb, d.Vb = (self.Kn_blk[i].data_ptr(), self.Vn_blk[i].data_ptr()) if dedup else (None, None)
+                d.uv_q = None if fold_uv[i][0] is None else fold_uv[i][0].data_ptr()
+                d.uv_qkv, d.uv_fc1 = fold_uv[i][1].data_ptr(), fold_uv[i][2].data_ptr()
+                for cname, t in (("carry_q", w["w_cproj"]), ("carry_cproj", w["w_proj"]), ("carry_fc1", w["w_fc2"]),
+                                 ("carry_fc2", blocks[i + 1]["w_q"] if i + 1 < m.depth else None)):
+                    cp, cn = ops._range(t) if t is not None and wpf == 2 else (None, 0)
+                    setattr(d, cname, cp)
+                    setattr(d, cname + "_bytes", cn)
+            fd["desc"], fd["desc_key"] = arr, dkey
+        f = _lib.DitForwardFold(
+            dtype=ops.dtype_code(self.dt), Be=self.Be, N=self.N, D=self.D, H=self.H, dh=self.dh, hidden=hid.shape[1], depth=m.depth,
+            L=self.L, nq_pad=self.nq_pad, nkv_pad_c=Kc.shape[2], nkv_pad_b=self.Kn_blk[0].shape[2] if dedup else 0,
+            b_from=self.B if dedup else self.Be, step=self.prow, n_steps=self.plan["t"].numel(), ln_eps=m.LN_EPS, scale=self.scale,
+            h=self.h.data_ptr(), xn=self.xn.data_ptr(), att=self.att.data_ptr(), hid=hid.data_ptr(), Qc=self.Qc.data_ptr(),
+            Qs=self.Qs.data_ptr(), Ks=self.Ks.data_ptr(), Vs=self.Vs.data_ptr(), mod=self.mod.data_ptr(),
+            center0=self.fcent[0].data_ptr(), center1=self.fcent[1].data_ptr(), part=self.fpart.data_ptr())
+        if with_kv:
+            f.kv_A, f.kv_W, f.kv_bias = self.y16.data_ptr(), pk["w_kv_all"].data_ptr(), pk["b_kv_all"].data_ptr()
+            f.kv_rows, f.kv_rows_per_batch, f.kv_K = Bkv * self.Lk, self.Lk, self.y16.shape[1]
+        if r.skip:
+            f.null_vrow = self.cs["vrow"].data_ptr()
+        return f, fd["desc"]
+
+    def single_launch(self, which: int, i: int, side: int, tag: str, flops: float) -> None:
+        # the skip's form of block i's to_q (1) or cross proj (2), which have no entry point of their own: ONE launch through
+        # primx_dit_blocks_fold (PrimxDitForwardFold::only_launch) - what the one-call route issues for that step
+        f, desc = self.fold_call(False)
+        f.only_block, f.only_launch, f.side = i, which, side
+        ops._dev(self.h, "h", torch.float32)
+        ops._timed(tag, flops, lambda: _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), desc, ops._stream()), "primx_dit_blocks_fold"))
+
+    def fc(self, b0: int, rows: slice, flip: int = 0):   # the (centre, scale) pairs the current site's producer used; flip = 1: where its
+        self.fside[b0] ^= flip                           # consumer leaves the next site's - the other array, which the next site then reads
+        return self.fcent[self.fside[b0]][rows]
+
+    def uv(self, i: int, s: int):                        # this call's (u, v) of block i's site s: rows of the planned loop's tables
+        return self.fold_uv[i][s][0, self.prow], self.fold_uv[i][s][1, self.prow]
+
+    def block(self, i: int, b0: int, b1: int, hook=None) -> None:
+        """DiTBlock i on batch entries [b0, b1) (dit_crossattn.py:51-58): 11 launches on the current stream, 8 with the LayerNorm fold."""
+        r, blocks, w, mod, hid, fside = self.r, self.blocks, self.blocks[i], self.mod, self.hid, self.fside
+        B, N, D, H, dh, L, scale, nq_pad, eps = self.B, self.N, self.D, self.H, self.dh, self.L, self.scale, self.nq_pad, self.m.LN_EPS
+        Qc, Qs, Ks, Vs, fc, uv, Kc_i, Vc_i = self.Qc, self.Qs, self.Ks, self.Vs, self.fc, self.uv, self.Kc_blk[i], self.Vc_blk[i]
+        by_ln, by_gemm = r.wpf == 1, r.wpf == 2          # `weight_prefetch`: carried by the LayerNorm launches or by the GEMM launches ahead
+        fuse, folded, skip, dedup = r.fuse, r.fold, r.skip, r.dedup
+        rows, Th = slice(b0 * N, b1 * N), (b1 - b0) * N
+        hh, xh, ah = self.h[rows], self.xn[rows], self.att[b0:b1]
+        m = mod[b0:b1, i * 9 * D:(i + 1) * 9 * D]
+        ch = [m[:, j * D:(j + 1) * D] for j in range(9)]  # shift/scale/gate x (mca, msa, mlp)
+        fp = self.fpart[rows] if folded else None
+        sy = None if self.sync is None else (self.sync[:self.sync_w] if b0 == 0 else self.sync[self.sync_w:])   # (`ln_in_kernel`)
+        # ---- cross-attention to the image tokens (dit_crossattn.py:55, attention.py:96-114)
+        if not fuse or i == 0:                       # (fused: the previous block's fc2 launch has normalised these rows)
+            # (the block's cross-attention K / V as the prefetch instead: -1.0 us on that kernel, +0.5 on this one)
+            ops.layernorm_modulate(hh, ch[0], ch[1], N, xh, eps, prefetch=(w["w_q"], w["w_cproj"]) if by_ln else ())
+            if folded:
+                fside[b0] = 0
+                ops.row_stats(hh, eps, fc(b0, rows))   # (centre, scale) of the first folded site: this LayerNorm's (mean, rstd)
+        bc = min(b1, B) if (r.collapse or skip) else b1   # batch entries [b0, bc) attend; [bc, b1) are unconditional rows
+        if bc > b0:
+            if folded and i > 0 and skip:            # (the consumer over the attending rows; it finishes the other rows' statistics)
+                self.single_launch(1, i, fside[b0], f"None {(bc - b0) * N}x{D}x{D}", 2.0 * (bc - b0) * N * D * D)
+                fside[b0] ^= 1
+            elif folded and i > 0:                   # (bc == b1, every row attends)
+                ops.linear_heads_fold(xh, w["w_q"], N, H, dh, [HEADS_ROWS], [Qc[b0:bc]], nq_pad, fp, *uv(i, 0), fc(b0, rows),
+                                      fc(b0, rows, 1), eps, scale0=scale, carry=w["w_cproj"] if by_gemm else None)
+            else:
+                ops.linear_heads(xh[:(bc - b0) * N], w["w_q"], w["b_q"], N, H, dh, [HEADS_ROWS], [Qc[b0:bc]], nq_pad,
+                                 scale0=scale, carry=w["w_cproj"] if by_gemm else None)
+            if dedup and bc > B:                     # entries [max(b0, B), bc) take the broadcast key / value entry
+                kc = Kc_i[b0:B] if b0 < B else None
+                ops.attention(Qc[b0:bc], kc, Vc_i[b0:B] if b0 < B else None, N, L, dh, scale, out=ah[:bc - b0],
+                              bcast=(self.Kn_blk[i], self.Vn_blk[i]))
+            else:
+                ops.attention(Qc[b0:bc], Kc_i[b0:bc], Vc_i[b0:bc], N, L, dh, scale, out=ah[:bc - b0])
+        if bc < b1 and skip and not folded:          # (unfolded: the value row is copied into the unconditional rows of `att`)
+            ah[max(bc, b0) - b0:].copy_(self.cs["vrow"][i].view(1, 1, D).expand(b1 - max(bc, b0), N, -1))
+        elif bc < b1 and not skip:
+            # V^T layout [b, h, DP, n_pad] (key 0 sits at position 0 of its quad-permuted group): the value row of every head
+            nb = b1 - max(bc, b0)
+            vsrc = self.Vn_blk[i].expand(nb, -1, -1, -1) if dedup else Vc_i[max(bc, b0):b1]
+            ah[max(bc, b0) - b0:].copy_(vsrc[:, :, :dh, 0].reshape(nb, 1, D).expand(-1, N, -1))
+        if hook is not None:
+            hook()
+        if folded and skip:                          # producer of the qkv site; the unconditional rows of A are the value row
+            self.single_launch(2, i, fside[b0], f"None {Th}x{D}x{D}", 2.0 * Th * D * D)
+        elif folded:                                 # producer of the qkv site
+            ops.linear_gate_residual_fold(ah.view(Th, D), w["w_cproj"], w["b_cproj"], ch[2], hh, N, ch[4], fc(b0, rows), xh, fp,
+                                          carry=w["w_proj"] if by_gemm else None)
+        else:
+            ops.linear_gate_residual(ah.view(Th, D), w["w_cproj"], w["b_cproj"], ch[2], hh, N, carry=w["w_proj"] if by_gemm else None,
+                                     ln=(ch[3], ch[4], xh, eps, sy) if fuse else None)
+        # ---- self-attention over the primitive tokens (dit_crossattn.py:56, attention.py:48-59)
+        if not fuse:
+            ops.layernorm_modulate(hh, ch[3], ch[4], N, xh, eps, prefetch=(w["w_proj"],) if by_ln else ())
+        if folded and r.ride_in_python and i + 1 < len(blocks):
+            # (`kv_ride`: the next block's to_k / to_v projection rides on this launch - what primx_dit_blocks_fold issues)
+            u1, v1 = uv(i, 1)
+            ops.linear_heads_fold_pair(dict(A=xh, W=w["w_qkv"], rows_per_batch=N, heads=H, dh=dh, kinds=[HEADS_ROWS, HEADS_KROWS, HEADS_VT],
+                                            dsts=[Qs[b0:b1], Ks[b0:b1], Vs[b0:b1]], n_pad=nq_pad, part=fp, u=u1, v=v1,
+                                            center=fc(b0, rows), center_out=fc(b0, rows, 1), eps=eps), *self.kv_problem(i + 1))
+        elif folded:
+            ops.linear_heads_fold(xh, w["w_qkv"], N, H, dh, [HEADS_ROWS, HEADS_KROWS, HEADS_VT], [Qs[b0:b1], Ks[b0:b1], Vs[b0:b1]],
+                                  nq_pad, fp, *uv(i, 1), fc(b0, rows), fc(b0, rows, 1), eps)
+        else:
+            ops.linear_heads(xh, w["w_qkv"], w["b_qkv"], N, H, dh, [HEADS_ROWS, HEADS_KROWS, HEADS_VT], [Qs[b0:b1], Ks[b0:b1], Vs[b0:b1]], nq_pad)
+        ops.attention(Qs[b0:b1], Ks[b0:b1], Vs[b0:b1], N, N, dh, scale, out=ah)
+        if folded:                                   # producer of the fc1 site
+            ops.linear_gate_residual_fold(ah.view(Th, D), w["w_proj"], w["b_proj"], ch[5], hh, N, ch[7], fc(b0, rows), xh, fp)
+        else:
+            ops.linear_gate_residual(ah.view(Th, D), w["w_proj"], w["b_proj"], ch[5], hh, N, ln=(ch[6], ch[7], xh, eps, sy) if fuse else None)
+        # ---- MLP (dit_crossattn.py:57, models/utils.py:94-101)
+        if not fuse:
+            ops.layernorm_modulate(hh, ch[6], ch[7], N, xh, eps, prefetch=(w["w_fc2"],) if by_ln else ())
+        if folded:
+            ops.linear_fold(xh, w["w_fc1"], hid[rows], fp, *uv(i, 2), fc(b0, rows), fc(b0, rows, 1), eps,
+                            act=ACT_GELU_TANH, carry=w["w_fc2"] if by_gemm else None)
+        else:
+            ops.linear(xh, w["w_fc1"], w["b_fc1"], out=hid[rows], act=ACT_GELU_TANH, carry=w["w_fc2"] if by_gemm else None)
+        last = i + 1 == len(blocks)
+        nxt = (self.fin_mod[0][b0:b1], self.fin_mod[1][b0:b1]) if last else \
+            (mod[b0:b1, (i + 1) * 9 * D:(i + 1) * 9 * D + D], mod[b0:b1, (i + 1) * 9 * D + D:(i + 1) * 9 * D + 2 * D])
+        if folded and not last:                      # producer of the next block's to_q site
+            ops.linear_gate_residual_fold(hid[rows], w["w_fc2"], w["b_fc2"], ch[8], hh, N, nxt[1], fc(b0, rows), xh, fp,
+                                          carry=blocks[i + 1]["w_q"] if by_gemm else None)
+        else:                                        # (the final layer's LayerNorm stays a launch: its Linear has 8 columns)
+            ops.linear_gate_residual(hid[rows], w["w_fc2"], w["b_fc2"], ch[8], hh, N,
+                                     carry=blocks[i + 1]["w_q"] if by_gemm and not last else None, ln=(*nxt, xh, eps, sy) if fuse else None)
+
+    def run_two_streams(self) -> None:
+        # Two HIP streams, one per CFG half (the conditional and the unconditional rows are independent chains of
+        # kernels): every GEMM of this path ends with a write burst that nothing of ITS OWN kernel can overlap
+        # (DESIGN_LOG.md section 4); with the second chain a few kernels behind the first, one chain's burst drains
+        # under the other chain's matrix phase.  Same kernels, same arithmetic per row.
+        main, side = torch.cuda.current_stream(), self.m._side_stream(self.h.device)
+        side.wait_stream(main)                       # embeddings, modulation and the K / V projection come first
+        lag = torch.cuda.Event()
+        for i in range(len(self.blocks)):
+            self.block(i, 0, self.B, hook=(lambda: lag.record(main)) if i == 0 else None)
+            with torch.cuda.stream(side):
+                if i == 0:
+                    side.wait_event(lag)             # the side chain starts when the main one is three kernels in
+                self.block(i, self.B, self.Be)
+        main.wait_stream(side)
+
+    def run_one_call(self) -> None:
+        # ONE foreign call for the forward's blocks (primx_dit_blocks_fold, ABI 24): the C side issues the launches block()
+        # would - same entry points, same arguments, same order, bit-identical results - at ~1 us of host time each instead of
+        # ~21 us of Python + ctypes (tools/host_bound_check.py).  The per-block descriptors are built once per planned loop.
+        f, desc = self.fold_call(self.r.ride)
+        ops._dev(self.h, "h", torch.float32)             # (the launch-device check of every op: ops._stream)
+        _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), desc, ops._stream()), "primx_dit_blocks_fold")
+
+    def run_block_loop(self) -> None:
+        probe, h, xn = self.m.block_probe, self.h, self.xn
+        for i in range(len(self.blocks)):
+            self.block(i, 0, self.Be)
+            if probe is not None:
+                rs = h.std(-1)
+                probe.append({
+                    "block": i, "folded": self.r.fold, "dtype": str(self.dt).replace("torch.", ""),
+                    "residual_abs_max": float(h.abs().max()), "row_std_min": float(rs.min()), "row_std_median": float(rs.median()),
+                    "row_std_max": float(rs.max()), "row_mean_abs_max": float(h.mean(-1).abs().max()),
+                    "next_operand_abs_max": float(xn.float().abs().max()), "next_operand_finite": bool(torch.isfinite(xn.float()).all())})
 
 
 class DiT(nn.Module):
@@ -163,8 +429,12 @@ class DiT(nn.Module):
         # accumulation leaves it.  The LayerNorm fold, the one-call route and the K / V riders carry it (include/primx_hip.h,
         # PrimxDitForwardFold::null_vrow).  Not with `cfg_streams` (each half is a chain of its own there).
         self.null_xattn_skip = os.environ.get("PRIMX_NULL_XATTN_SKIP", "1") != "0"
-        # `null_kv_once` (default on): a forward that skips reads nothing of the broadcast K / V entry once its conditioning state
-        # holds the value rows, so it does not project that entry again (_forward16, `reads_null`); False projects it in every forward
+        # `null_kv_once` (default on; False projects the entry in every forward).  The broadcast entry Kn / Vn depends on the null
+        # embedding and the packed weights only.  Its readers: the broadcast attention and the value-row gather of a forward that does
+        # not skip, and _Forward16.null_value_rows.  A forward that skips and finds the value rows of its conditioning state reads
+        # nothing of it and does not project it (_route16, `reads_null`; one 44 us launch per forward at DiT-XL); a forward that reads
+        # it projects it as before, and where the conditional projection is reused (`reuse_cond_kv`) it projects the entry unless this
+        # conditioning state was the last to do so.
         self.null_kv_once = True
         # `collapse_null_cross_attention`: the opt-in from before the skip (round 3) - the same shortcut without `dedup_null_kv`
         # and without the -0 rule ("exact algebra up to rounding"); unfolded forwards only, a folded forward ignores it.
@@ -180,14 +450,23 @@ class DiT(nn.Module):
         # entries with keys of their own and runs the unsplit kernel, the default route splits the keys inside the workgroup
         # (csrc/attention.hip, KSPLIT) - the two differ at rounding level, inside the same contract.)
         self.dedup_null_kv = os.environ.get("PRIMX_NULL_KV_DEDUP", "1") != "0"
-        # weight prefetch of the loader-wave GEMMs (_forward16): 2 = carried by the GEMM launches one or two ahead, 1 = carried by the
-        # LayerNorm launches, 0 = off (PRIMX_WPREFETCH)
+        # Weight prefetch (PRIMX_WPREFETCH=0 turns it off): the 1.8 GB of weights stream through HBM once per forward, and the
+        # 128 x 144 GEMMs run 2 - 4 us longer with cold weights than with cache-resident ones (rocprofv3, tools/gpu/r3_touch.sh).
+        # `weight_prefetch` = 1: every LayerNorm launch - a short kernel that reads the residual stream from the Infinity Cache -
+        # carries the prefetch of the weights of the loader-wave GEMMs that follow it (ops.layernorm_modulate `prefetch=`): no
+        # launch, no event, no stream of its own.  `weight_prefetch` = 2 (the default): the GEMM launches carry it instead (`carry=`):
+        # the compute waves of a loader-wave kernel touch the lines of a LATER GEMM's weights in front of their k-loop - to_q
+        # carries cproj's weights, cproj proj's, fc1 fc2's, fc2 the next block's to_q - and the LayerNorms keep to their own bytes.
         self.weight_prefetch = int(os.environ.get("PRIMX_WPREFETCH", "2"))
-        # the LayerNorm + modulate that follows every gated residual add is requested from the SAME entry point as the GEMM
-        # (primx_linear_gate_residual_ln; PRIMX_DIT_FUSE_LN=0: separate primx_layernorm_modulate calls).  `ln_in_kernel`
-        # (PRIMX_DIT_LN_TAIL=1) additionally hands the library the sync words that let it run the LayerNorm in the TAIL of the GEMM
-        # kernel: bit-identical, and measured SLOWER than the launch it saves in every arrival protocol tried in round 4 (10.25 vs
-        # 8.99 ms per step at best, DESIGN.md section 4 / DESIGN_LOG.md section 10) - off by default, kept as a measured experiment.
+        # `fuse_ln` (round 4; PRIMX_DIT_FUSE_LN=0: separate primx_layernorm_modulate calls): every gated residual add of a block is
+        # followed by the LayerNorm + modulate of the next branch (dit_crossattn.py:55-57) - of the next block after fc2, of the final
+        # layer after the last one - so both are requested from one entry point, ops.linear_gate_residual(ln=...)
+        # (primx_linear_gate_residual_ln): bit-identical to the separate calls, and only the FIRST LayerNorm of a forward is a call of
+        # its own.  Not with the LayerNorm-carried prefetch (`weight_prefetch` = 1: that mode needs the LayerNorm launches to carry the
+        # ranges).  Whether the library runs the LayerNorm as a second launch (default) or in the TAIL of the GEMM kernel is decided by
+        # the sync words, which `ln_in_kernel` (PRIMX_DIT_LN_TAIL=1) hands it: bit-identical, and measured SLOWER than the launch it
+        # saves in every arrival protocol tried in round 4 (10.25 vs 8.99 ms per step at best, DESIGN.md section 4 / DESIGN_LOG.md
+        # section 10) - off by default, kept as a measured experiment.
         self.fuse_ln = os.environ.get("PRIMX_DIT_FUSE_LN", "1") != "0"
         self.ln_in_kernel = os.environ.get("PRIMX_DIT_LN_TAIL", "0") == "1"
         self._ln_sync: Dict = {}              # device -> int32 workspace of the fused route (zero between launches)
@@ -254,13 +533,7 @@ class DiT(nn.Module):
         self._packed_only = False
 
     def _apply(self, fn, *a, **k):
-        self.__dict__["_pack"] = {}
-        self.__dict__["_heads_ws"] = {}
-        self.__dict__["_heads_owner"] = {}
-        self.__dict__["_heads_lru"] = []
-        self.__dict__["_heads_group"] = None
-        self.__dict__["_cond"] = None
-        self.__dict__["_t_plan"] = None
+        self.__dict__.update(_pack={}, _heads_ws={}, _heads_owner={}, _heads_lru=[], _heads_group=None, _cond=None, _t_plan=None)
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
@@ -678,29 +951,72 @@ class DiT(nn.Module):
         A[:, :, 1] = v[:, :, :, 0].permute(1, 2, 0, 3)
         return A
 
+    def _kv_operands(self, Bkv: int, L: int, Lk: int, dt, dev):
+        # cross-attention K / V of every block in ONE projection GEMM (N = depth * 2D): [depth*Bkv, H, L_pad, DP]
+        kv_pad = 256 if Lk != L else ops.BKV
+        return tuple(self._heads(tag, self.depth * Bkv, L, kind, dt, dev, kv_pad) for tag, kind in (("Kc", HEADS_KROWS), ("Vc", HEADS_VT)))
+
+    def _kv_cached(self, cs: Dict, L: int, dt, dev, Bkv: int) -> bool:   # `reuse_cond_kv`: does `cs` hold the projection, in this forward's operands?
+        Kc, Vc = self._kv_operands(Bkv, L, cs["Lk"], dt, dev) if self.reuse_cond_kv and cs["kv_valid"] else (None, None)
+        return Kc is not None and cs.get("kv_id") == (Kc.data_ptr(), Vc.data_ptr())
+
+    def _route16(self, B, N, L, Lk, D, H, depth, Dc, null_half, has_null_entry, plan_row, plan_steps, profiling, probing,
+                 kv_cached, vrow_cached, fold_ok, pair_fits, caps) -> _Route16:
+        """Every decision of a 16-bit forward, from plain Python values and the switches as `self` holds them now: no tensor, no library
+        call, so tests/test_dit_routes_cpu.py asks it without a GPU.  `kv_cached(Bkv)`, `fold_ok(T, N)` and `pair_fits(T, N, D, H, kv_rows,
+        Lk, Dc)` are asked only where the answer matters; `caps` = _lib.capabilities()."""
+        Be, dh = 2 * B if null_half else B, D // H
+        # (dedup: the operands hold the B conditional entries only; the unconditional ones share the broadcast entry Kn / Vn)
+        dedup = bool(self.dedup_null_kv) and null_half and has_null_entry and depth > 0
+        Bkv = B if dedup else Be
+        two_streams = bool(self.cfg_streams) and null_half and depth > 0 and not profiling
+        wpf = int(self.weight_prefetch)
+        fuse = bool(self.fuse_ln) and wpf != 1           # (not with the LayerNorm-carried prefetch: see `fuse_ln` in __init__)
+        ln_tail = fuse and bool(self.ln_in_kernel)       # (this alone decides whether the sync words are allocated and passed)
+        # the LayerNorm fold (`fold_ln`): planned calls only - u / v come from the loop's tables, shared by all batch entries
+        fold = bool(plan_row is not None and fuse and not (self.cfg_streams and null_half and not profiling)
+                    and plan_steps <= self.fold_max_steps and fold_ok(Be * N, N))
+        # `null_xattn_skip`: the unconditional entries' to_q and attention walk are not run (see __init__).  Only at the head dims
+        # whose kernel forms tests/test_hip_null_identity.py holds to the value-row property (72: max carried in Q's spare columns;
+        # 64, 32: whole fragments) - any other head dim walks as before; D % 8: the value rows are read in 16-byte pieces.  The
+        # skip's GEMM forms under the fold are whole row tiles - the unconditional rows start at a tile boundary of either tile: a
+        # precondition of those forms stated here, not a live branch (fold_ok already asks N % 256 == 0)
+        skip = (bool(self.null_xattn_skip) and dedup and not two_streams and dh in self.NULL_SKIP_HEAD_DIMS and D % 8 == 0
+                and "null_skip" in caps and not (fold and (B * N) % 256))
+        # (the round-3 opt-in: unfolded forwards that do not already skip)
+        collapse = bool(self.collapse_null_cross_attention) and null_half and not fold and not skip
+        one_call = bool(not two_streams and fold and self.blocks_call and not ln_tail and not profiling and not probing
+                        and "blocks_call" in caps)
+        need_kv = depth > 0 and not kv_cached(Bkv)
+        # `kv_ride`: every folded single-stream forward - the library issues the riders on the one-call route, the block loop
+        # otherwise - where the riders fit the qkv launch's round (T = 4096: 192 + 48 tiles; a large batch fills the chip by itself
+        # and keeps the batched projection)
+        ride = bool(need_kv and self.kv_ride and fold and not two_streams and "kv_ride" in caps
+                    and pair_fits(Be * N, N, D, H, Bkv * Lk, Lk, Dc))
+        reads_null = dedup and not (self.null_kv_once and skip and vrow_cached)    # (`null_kv_once` in __init__: who reads the broadcast entry)
+        return _Route16(dedup, Bkv, two_streams, fuse, ln_tail, fold, skip, collapse, one_call, need_kv, ride, ride and not one_call,
+                        reads_null, wpf)
+
     def _forward16(self, x, t, y, dt, null_half: bool):
         """The 16-bit autocast path.  `null_half`: classifier-free guidance - the effective batch is [x; x] with the
         second half conditioned on the null embedding (dit_crossattn.py:204-209), assembled here without materialising
-        the concatenations: tokens are embedded into both halves of the residual stream, t is embedded once."""
+        the concatenations: tokens are embedded into both halves of the residual stream, t is embedded once.  (_route16 decides,
+        _Forward16 holds the operands and launches.)"""
         B, N, Cin = x.shape
         Be = 2 * B if null_half else B
-        L, Dc = y.shape[1], y.shape[2]
-        D, H = self.hidden_size, self.num_heads
-        dh = D // H
-        T = Be * N
-        pk = self.packed(dt)
-        dev = x.device
+        L, Dc, D, H = y.shape[1], y.shape[2], self.hidden_size, self.num_heads
+        pk, dev = self.packed(dt), x.device
         self._heads_begin((Be, N, L, dt, str(dev)))
-
         xf = x.reshape(B * N, Cin).float().contiguous()
-        h = torch.empty(T, D, dtype=torch.float32, device=dev)
+        h = torch.empty(Be * N, D, dtype=torch.float32, device=dev)
         # cat([x, x]) embeds to the same rows twice (dit_crossattn.py:205,191): the embedding kernel writes both halves
         self._embed_tokens(xf, h[:B * N], h[B * N:] if null_half else None)
         plan = self._t_plan
-        if plan is not None and plan["row"] is not None:
+        prow = plan["row"] if plan is not None else None
+        if prow is not None:
             # the sampling loop announced its timesteps (plan_timesteps): this call's modulation is a row of the per-loop
             # table, shared by all batch entries (row stride 0)
-            mod = self._modulation_table(plan, dt, pk)[plan["row"]:plan["row"] + 1].expand(Be, -1)
+            mod = self._modulation_table(plan, dt, pk)[prow:prow + 1].expand(Be, -1)
         else:
             t_emb = self.t_embedder(t)                               # [B, D]
             st16 = torch.empty(Be, D, dtype=dt, device=dev)
@@ -711,338 +1027,22 @@ class DiT(nn.Module):
             mod = ops.linear(st16, pk["w_ada"], pk["b_ada"])         # [Be, depth*9D + 2D]
         cs = self._cond_state(y, null_half, dt)
         cs["group"] = self._heads_group
-        Lk, y16 = cs["Lk"], cs["y16"]
-
-        nq_pad = ops.round_up(N, ops.BQ)
-        Qc = self._heads("Qc", Be, N, HEADS_ROWS, dt, dev, ops.BQ)
-        # cross-attention K / V of every block in ONE projection GEMM (N = depth * 2D): [depth*Be, H, L_pad, DP]
-        kv_pad = 256 if Lk != L else ops.BKV
-        # (dedup: the operands hold the B conditional entries only; the unconditional ones share the broadcast entry Kn / Vn)
-        dedup = bool(self.dedup_null_kv) and null_half and cs["null16"] is not None and self.depth > 0
-        Bkv = B if dedup else Be
-        Kc = self._heads("Kc", self.depth * Bkv, L, HEADS_KROWS, dt, dev, kv_pad)
-        Vc = self._heads("Vc", self.depth * Bkv, L, HEADS_VT, dt, dev, kv_pad)
-        Kc_blk = Kc.view(self.depth, Bkv, *Kc.shape[1:])
-        Vc_blk = Vc.view(self.depth, Bkv, *Vc.shape[1:])
-        Kn_blk = Vn_blk = None
-        if dedup:
-            Ln = ops.bcast_keys(L)
-            Kn = self._heads("Kn", self.depth, Ln, HEADS_KROWS, dt, dev, ops.BKV)
-            Vn = self._heads("Vn", self.depth, Ln, HEADS_VT, dt, dev, ops.BKV)
-            Kn_blk, Vn_blk = Kn.view(self.depth, 1, *Kn.shape[1:]), Vn.view(self.depth, 1, *Vn.shape[1:])
-        need_kv = bool(self.depth) and not (self.reuse_cond_kv and cs["kv_valid"] and cs.get("kv_id") == (Kc.data_ptr(), Vc.data_ptr()))
-        two_streams = bool(self.cfg_streams and null_half and self.depth and ops.PROFILE is None)
-        # `null_xattn_skip`: the unconditional entries' to_q and attention walk are not run (see __init__).  Only at the head dims
-        # whose kernel forms tests/test_hip_null_identity.py holds to the value-row property (72: max carried in Q's spare columns;
-        # 64, 32: whole fragments) - any other head dim walks as before; D % 8: the value rows are read in 16-byte pieces
-        skip = (bool(self.null_xattn_skip) and dedup and not two_streams and dh in self.NULL_SKIP_HEAD_DIMS and D % 8 == 0
-                and _lib.null_skip_available())
-
-        def null_value_rows() -> torch.Tensor:
-            # [depth, D] 16-bit: per block the value row of the H heads side by side, out of the broadcast entry's V^T layout [1, H, DP,
-            # n_pad] (key 0 sits at position 0 of its quad-permuted group), -0 -> +0 on the bit pattern (0x8000 in both 16-bit types)
-            bits = Vn.view(self.depth, H, Vn.shape[2], Vn.shape[3])[:, :, :dh, 0].view(torch.int16)
-            return torch.where(bits == -32768, 0, bits).reshape(self.depth, D).contiguous().view(dt)
-
-        ride_state = {"on": False}
-
-        def kv_problem(i: int):
-            # block i's [to_k; to_v] projection of the conditional entries as the heads GEMM primx_linear_heads_fold_pair carries
-            wkv, bkv = pk["w_kv_all"][i * 2 * D:(i + 1) * 2 * D], pk["b_kv_all"][i * 2 * D:(i + 1) * 2 * D]
-            return (y16[:Bkv * Lk], wkv, bkv, Lk, H, dh, [HEADS_KROWS, HEADS_VT], [Kc_blk[i], Vc_blk[i]], Kc.shape[2], 1.0, Bkv * L)
-
-        # `null_kv_once`: who last projected the broadcast entry is written ON the buffers (the token of the conditioning state): a new
-        # buffer from _heads carries no token, a buffer shared with another conditioning state (the key of Kn / Vn does not depend on
-        # the batch size) carries that one's, and repack() drops the buffers and the state alike - each reads as "not valid"
-        def null_kv_valid() -> bool:
-            tok = cs.get("null_tok")
-            return tok is not None and getattr(Kn, "_primx_null_tok", None) is tok and getattr(Vn, "_primx_null_tok", None) is tok
-
-        def project_null_kv() -> None:
-            ops.linear_heads(cs["null16"], pk["w_kv_all"], pk["b_kv_all"], Ln, H, dh, [HEADS_KROWS, HEADS_VT], [Kn, Vn],
-                             Kn.shape[2], n_rep=self.depth, rep_batches=1)
-            Kn._primx_null_tok = Vn._primx_null_tok = cs.setdefault("null_tok", object())
-
-        def project_kv(cond_rows: bool, null_rows: bool) -> None:
-            # (cond_rows False: the one-call route projects the conditional entries itself - `kv_ride`; null_rows False: nothing of
-            # this forward reads the broadcast entry)
-            if cond_rows:
-                ops.linear_heads(y16[:Bkv * Lk], pk["w_kv_all"], pk["b_kv_all"], Lk, H, dh, [HEADS_KROWS, HEADS_VT], [Kc, Vc],
-                                 Kc.shape[2], n_rep=self.depth, rep_batches=Bkv, real_rows=Bkv * L)
-            if null_rows:
-                project_null_kv()
-            cs["kv_valid"], cs["kv_id"] = True, (Kc.data_ptr(), Vc.data_ptr())
-        Qs = self._heads("Qs", Be, N, HEADS_ROWS, dt, dev, ops.BQ)
-        Ks = self._heads("Ks", Be, N, HEADS_KROWS, dt, dev, ops.BQ)
-        Vs = self._heads("Vs", Be, N, HEADS_VT, dt, dev, ops.BQ)
-        xn = torch.empty(T, D, dtype=dt, device=dev)
-        att = torch.empty(Be, N, D, dtype=dt, device=dev)
-        hid = torch.empty(T, pk["blocks"][0]["w_fc1"].shape[0], dtype=dt, device=dev) if self.depth else None
-        scale = dh ** -0.5
-
-        # Weight prefetch (PRIMX_WPREFETCH=0 turns it off): the 1.8 GB of weights stream through HBM once per forward, and the
-        # 128 x 144 GEMMs run 2 - 4 us longer with cold weights than with cache-resident ones (rocprofv3, tools/gpu/r3_touch.sh).
-        # `weight_prefetch` = 1: every LayerNorm launch - a short kernel that reads the residual stream from the Infinity Cache -
-        # carries the prefetch of the weights of the loader-wave GEMMs that follow it (ops.layernorm_modulate `prefetch=`): no
-        # launch, no event, no stream of its own.  `weight_prefetch` = 2 (the default): the GEMM launches carry it instead (`carry=`):
-        # the compute waves of a loader-wave kernel touch the lines of a LATER GEMM's weights in front of their k-loop - to_q
-        # carries cproj's weights, cproj proj's, fc1 fc2's, fc2 the next block's to_q - and the LayerNorms keep to their own bytes.
-        wpf = int(self.weight_prefetch)
-        blocks = pk["blocks"]
-        # `fuse_ln` (round 4): every gated residual add of a block is followed by the LayerNorm + modulate of the next branch
-        # (dit_crossattn.py:55-57) - of the next block after fc2, of the final layer after the last one - so both are requested
-        # from one entry point, ops.linear_gate_residual(ln=...): bit-identical to the separate calls, and only the FIRST LayerNorm
-        # of a forward is a call of its own.  Whether the library runs the LayerNorm as a second launch (default) or in the tail of
-        # the GEMM kernel is decided by the `sync` words (`ln_in_kernel`).  Not with the LayerNorm-carried prefetch (wpf == 1: that
-        # mode needs the LayerNorm launches to carry the ranges).
-        fuse = bool(self.fuse_ln) and wpf != 1
-        sync = None
-        sync_w = ops.ln_sync_words(T)
-        if fuse and self.ln_in_kernel:
-            # (two regions: with `cfg_streams` the two halves run concurrently and must not share words)
-            key = str(dev)
-            sync = self._ln_sync.get(key)
-            if sync is None or sync.numel() < 2 * sync_w:
-                sync = self._ln_sync[key] = torch.zeros(2 * sync_w, dtype=torch.int32, device=dev)
-        base = self.depth * 9 * D
-        fin_mod = (mod[:, base:base + D], mod[:, base + D:base + 2 * D])    # final layer's shift / scale
-        # the LayerNorm fold (`fold_ln`): planned calls only - u / v come from the loop's tables, shared by all batch entries
-        fold_uv = fcent = fpart = None
-        prow = plan["row"] if plan is not None else None
-        if (prow is not None and fuse and not (self.cfg_streams and null_half and ops.PROFILE is None)
-                and plan["t"].numel() <= self.fold_max_steps and self._fold_ok(T, N)):
-            fold_uv = self._fold_tables(plan, dt, pk)["uv"]
-            if dt == torch.float16:
-                self._fold_fp16_used = True
-            wk = (str(dev), T)
-            if wk not in self._fold_ws:
-                self._fold_ws = {wk: ops.fold_workspace(T, D, dev)}
-            fcent, fpart = self._fold_ws[wk]
-        # (the round-3 opt-in: unfolded forwards that do not already skip)
-        collapse = bool(self.collapse_null_cross_attention) and null_half and fold_uv is None and not skip
-        # the skip's GEMM forms are whole row tiles: the unconditional rows start at a tile boundary of either tile
-        if skip and fold_uv is not None and (B * N) % 256:
-            skip = False
-
-        fside: Dict[int, int] = {}                       # per row range (its b0): which of the fold's two (centre, scale) arrays the current site reads
-
-        def warm(*wts):
-            return wts if wpf == 1 else ()
-
-        def carry(wt):
-            return wt if wpf == 2 else None
-
-        def fold_call(with_kv: bool):
-            # the arguments of primx_dit_blocks_fold: this forward's struct and the per-block descriptors (built once per planned loop)
-            fd = plan["fold"]
-            dkey = (Kc.data_ptr(), Vc.data_ptr(), Kn_blk[0].data_ptr() if dedup else 0, wpf, Bkv)
-            if fd.get("desc_key") != dkey:
-                arr = (_lib.DitBlockFold * self.depth)()
-                rng = lambda t: ops._range(t) if wpf == 2 else (None, 0)
-                for i, w in enumerate(blocks):
-                    d = arr[i]
-                    for name in ("w_q", "b_q", "w_cproj", "b_cproj", "w_qkv", "w_proj", "b_proj", "w_fc1", "w_fc2", "b_fc2"):
-                        setattr(d, name, None if w[name] is None else w[name].data_ptr())
-                    d.Kc, d.Vc = Kc_blk[i].data_ptr(), Vc_blk[i].data_ptr()
-                    d.Kb, d.Vb = (Kn_blk[i].data_ptr(), Vn_blk[i].data_ptr()) if dedup else (None, None)
-                    d.uv_q = None if fold_uv[i][0] is None else fold_uv[i][0].data_ptr()
-                    d.uv_qkv, d.uv_fc1 = fold_uv[i][1].data_ptr(), fold_uv[i][2].data_ptr()
-                    for cname, t in (("carry_q", w["w_cproj"]), ("carry_cproj", w["w_proj"]), ("carry_fc1", w["w_fc2"]),
-                                     ("carry_fc2", blocks[i + 1]["w_q"] if i + 1 < self.depth else None)):
-                        cp, cn = rng(t) if t is not None else (None, 0)
-                        setattr(d, cname, cp)
-                        setattr(d, cname + "_bytes", cn)
-                fd["desc"], fd["desc_key"] = arr, dkey
-            f = _lib.DitForwardFold(
-                dtype=ops.dtype_code(dt), Be=Be, N=N, D=D, H=H, dh=dh, hidden=hid.shape[1], depth=self.depth, L=L, nq_pad=nq_pad,
-                nkv_pad_c=Kc.shape[2], nkv_pad_b=Kn_blk[0].shape[2] if dedup else 0, b_from=B if dedup else Be, step=prow,
-                n_steps=plan["t"].numel(), ln_eps=self.LN_EPS, scale=scale, h=h.data_ptr(), xn=xn.data_ptr(), att=att.data_ptr(),
-                hid=hid.data_ptr(), Qc=Qc.data_ptr(), Qs=Qs.data_ptr(), Ks=Ks.data_ptr(), Vs=Vs.data_ptr(), mod=mod.data_ptr(),
-                center0=fcent[0].data_ptr(), center1=fcent[1].data_ptr(), part=fpart.data_ptr())
-            if with_kv:
-                f.kv_A, f.kv_W, f.kv_bias = y16.data_ptr(), pk["w_kv_all"].data_ptr(), pk["b_kv_all"].data_ptr()
-                f.kv_rows, f.kv_rows_per_batch, f.kv_K = Bkv * Lk, Lk, Dc
-            if skip:
-                f.null_vrow = cs["vrow"].data_ptr()
-            return f, fd["desc"]
-
-        def single_launch(which: int, i: int, side: int, tag: str, flops: float) -> None:
-            # the skip's form of block i's to_q (1) or cross proj (2), which have no entry point of their own: ONE launch through
-            # primx_dit_blocks_fold (PrimxDitForwardFold::only_launch) - what the one-call route issues for that step
-            f, desc = fold_call(False)
-            f.only_block, f.only_launch, f.side = i, which, side
-            ops._dev(h, "h", torch.float32)
-            ops._timed(tag, flops, lambda: _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), desc, ops._stream()),
-                                                      "primx_dit_blocks_fold"))
-
-        def block(i, w, b0, b1, hook=None):
-            """DiTBlock i on batch entries [b0, b1) (dit_crossattn.py:51-58): 11 launches on the current stream, 8 with the LayerNorm fold."""
-            r0, r1 = b0 * N, b1 * N
-            hh, xh, ah = h[r0:r1], xn[r0:r1], att[b0:b1]
-            Th = r1 - r0
-            m = mod[b0:b1, i * 9 * D:(i + 1) * 9 * D]
-            ch = [m[:, j * D:(j + 1) * D] for j in range(9)]  # shift/scale/gate x (mca, msa, mlp)
-            def ln_of(shift, scale):                     # the LayerNorm that follows a gated residual add, fused into its GEMM
-                if not fuse:
-                    return None
-                return (shift, scale, xh, self.LN_EPS, None if sync is None else (sync[:sync_w] if b0 == 0 else sync[sync_w:]))
-            # ---- cross-attention to the image tokens (dit_crossattn.py:55, attention.py:96-114)
-            folded = fold_uv is not None
-            fp = fpart[r0:r1] if folded else None
-            uvs = fold_uv[i] if folded else None
-
-            def fc_in():                                 # the (centre, scale) pairs the current site's producer used ...
-                return fcent[fside[b0]][r0:r1]
-
-            def fc_flip():                               # ... and where its consumer leaves the next site's: the other array
-                fside[b0] ^= 1
-                return fcent[fside[b0]][r0:r1]
-
-            def uv(s):                                   # this call's (u, v) of site s: rows of the planned loop's tables
-                return uvs[s][0, prow], uvs[s][1, prow]
-            if not fuse or i == 0:                       # (fused: the previous block's fc2 launch has normalised these rows)
-                # (the block's cross-attention K / V as the prefetch instead: -1.0 us on that kernel, +0.5 on this one)
-                ops.layernorm_modulate(hh, ch[0], ch[1], N, xh, self.LN_EPS, prefetch=warm(w["w_q"], w["w_cproj"]))
-                if folded:
-                    fside[b0] = 0
-                    ops.row_stats(hh, self.LN_EPS, fc_in())   # (centre, scale) of the first folded site: this LayerNorm's (mean, rstd)
-            bc = min(b1, B) if (collapse or skip) else b1   # batch entries [b0, bc) attend; [bc, b1) are unconditional rows
-            if bc > b0:
-                if folded and i > 0 and skip:            # (the consumer over the attending rows; it finishes the other rows' statistics)
-                    single_launch(1, i, fside[b0], f"None {(bc - b0) * N}x{D}x{D}", 2.0 * (bc - b0) * N * D * D)
-                    fside[b0] ^= 1
-                elif folded and i > 0:                   # (bc == b1, every row attends)
-                    ops.linear_heads_fold(xh, w["w_q"], N, H, dh, [HEADS_ROWS], [Qc[b0:bc]], nq_pad, fp, *uv(0), fc_in(), fc_flip(),
-                                          self.LN_EPS, scale0=scale, carry=carry(w["w_cproj"]))
-                else:
-                    ops.linear_heads(xh[:(bc - b0) * N], w["w_q"], w["b_q"], N, H, dh, [HEADS_ROWS], [Qc[b0:bc]], nq_pad,
-                                     scale0=scale, carry=carry(w["w_cproj"]))
-                if dedup and bc > B:                     # entries [max(b0, B), bc) take the broadcast key / value entry
-                    kc = Kc_blk[i][b0:B] if b0 < B else None
-                    ops.attention(Qc[b0:bc], kc, Vc_blk[i][b0:B] if b0 < B else None, N, L, dh, scale, out=ah[:bc - b0],
-                                  bcast=(Kn_blk[i], Vn_blk[i]))
-                else:
-                    ops.attention(Qc[b0:bc], Kc_blk[i][b0:bc], Vc_blk[i][b0:bc], N, L, dh, scale, out=ah[:bc - b0])
-            if bc < b1 and skip and not folded:          # (unfolded: the value row is copied into the unconditional rows of `att`)
-                ah[max(bc, b0) - b0:].copy_(cs["vrow"][i].view(1, 1, D).expand(b1 - max(bc, b0), N, -1))
-            elif bc < b1 and not skip:
-                # V^T layout [b, h, DP, n_pad] (key 0 sits at position 0 of its quad-permuted group): the value row of every head
-                nb = b1 - max(bc, b0)
-                vsrc = Vn_blk[i].expand(nb, -1, -1, -1) if dedup else Vc_blk[i][max(bc, b0):b1]
-                vrow = vsrc[:, :, :dh, 0].reshape(nb, 1, D)
-                ah[max(bc, b0) - b0:].copy_(vrow.expand(-1, N, -1))
-            if hook is not None:
-                hook()
-            if folded and skip:                          # producer of the qkv site; the unconditional rows of A are the value row
-                single_launch(2, i, fside[b0], f"None {Th}x{D}x{D}", 2.0 * Th * D * D)
-            elif folded:                                 # producer of the qkv site
-                ops.linear_gate_residual_fold(ah.view(Th, D), w["w_cproj"], w["b_cproj"], ch[2], hh, N, ch[4], fc_in(), xh, fp,
-                                              carry=carry(w["w_proj"]))
-            else:
-                ops.linear_gate_residual(ah.view(Th, D), w["w_cproj"], w["b_cproj"], ch[2], hh, N, carry=carry(w["w_proj"]),
-                                         ln=ln_of(ch[3], ch[4]))
-            # ---- self-attention over the primitive tokens (dit_crossattn.py:56, attention.py:48-59)
-            if not fuse:
-                ops.layernorm_modulate(hh, ch[3], ch[4], N, xh, self.LN_EPS, prefetch=warm(w["w_proj"]))
-            if folded and ride_state["on"] and i + 1 < len(blocks):
-                # (`kv_ride`: the next block's to_k / to_v projection rides on this launch - what primx_dit_blocks_fold issues)
-                u1, v1 = uv(1)
-                ops.linear_heads_fold_pair(dict(A=xh, W=w["w_qkv"], rows_per_batch=N, heads=H, dh=dh, kinds=[HEADS_ROWS, HEADS_KROWS, HEADS_VT],
-                                                dsts=[Qs[b0:b1], Ks[b0:b1], Vs[b0:b1]], n_pad=nq_pad, part=fp, u=u1, v=v1, center=fc_in(),
-                                                center_out=fc_flip(), eps=self.LN_EPS), *kv_problem(i + 1))
-            elif folded:
-                ops.linear_heads_fold(xh, w["w_qkv"], N, H, dh, [HEADS_ROWS, HEADS_KROWS, HEADS_VT],
-                                      [Qs[b0:b1], Ks[b0:b1], Vs[b0:b1]], nq_pad, fp, *uv(1), fc_in(), fc_flip(), self.LN_EPS)
-            else:
-                ops.linear_heads(xh, w["w_qkv"], w["b_qkv"], N, H, dh, [HEADS_ROWS, HEADS_KROWS, HEADS_VT],
-                                 [Qs[b0:b1], Ks[b0:b1], Vs[b0:b1]], nq_pad)
-            ops.attention(Qs[b0:b1], Ks[b0:b1], Vs[b0:b1], N, N, dh, scale, out=ah)
-            if folded:                                   # producer of the fc1 site
-                ops.linear_gate_residual_fold(ah.view(Th, D), w["w_proj"], w["b_proj"], ch[5], hh, N, ch[7], fc_in(), xh, fp)
-            else:
-                ops.linear_gate_residual(ah.view(Th, D), w["w_proj"], w["b_proj"], ch[5], hh, N, ln=ln_of(ch[6], ch[7]))
-            # ---- MLP (dit_crossattn.py:57, models/utils.py:94-101)
-            if not fuse:
-                ops.layernorm_modulate(hh, ch[6], ch[7], N, xh, self.LN_EPS, prefetch=warm(w["w_fc2"]))
-            if folded:
-                ops.linear_fold(xh, w["w_fc1"], hid[r0:r1], fp, *uv(2), fc_in(), fc_flip(), self.LN_EPS, act=ACT_GELU_TANH,
-                                carry=carry(w["w_fc2"]))
-            else:
-                ops.linear(xh, w["w_fc1"], w["b_fc1"], out=hid[r0:r1], act=ACT_GELU_TANH, carry=carry(w["w_fc2"]))
-            last = i + 1 == len(blocks)
-            nxt = (fin_mod[0][b0:b1], fin_mod[1][b0:b1]) if last else \
-                (mod[b0:b1, (i + 1) * 9 * D:(i + 1) * 9 * D + D], mod[b0:b1, (i + 1) * 9 * D + D:(i + 1) * 9 * D + 2 * D])
-            if folded and not last:                      # producer of the next block's to_q site
-                ops.linear_gate_residual_fold(hid[r0:r1], w["w_fc2"], w["b_fc2"], ch[8], hh, N, nxt[1], fc_in(), xh, fp,
-                                              carry=carry(blocks[i + 1]["w_q"]))
-            else:                                        # (the final layer's LayerNorm stays a launch: its Linear has 8 columns)
-                ops.linear_gate_residual(hid[r0:r1], w["w_fc2"], w["b_fc2"], ch[8], hh, N,
-                                         carry=None if last else carry(blocks[i + 1]["w_q"]), ln=ln_of(*nxt))
-
-        one_call = (not two_streams and fold_uv is not None and self.blocks_call and sync is None and ops.PROFILE is None
-                    and self.block_probe is None and _lib.blocks_call_available())
-        # `kv_ride`: every folded single-stream forward - the library issues the riders on the one-call route, the block loop below otherwise
-        # - where the riders fit the qkv launch's round (T = 4096: 192 + 48 tiles; a large batch fills the chip by itself and keeps the
-        # batched projection)
-        ride = (need_kv and self.kv_ride and fold_uv is not None and not two_streams and _lib.kv_ride_available()
-                and ops.fold_pair_fits(T, N, D, H, Bkv * Lk, Lk, Dc))
-        ride_state["on"] = ride and not one_call
-        # The broadcast entry Kn / Vn depends on the null embedding and the packed weights only.  Its readers: the broadcast attention
-        # and the value-row gather of a forward that does not skip, and null_value_rows() below.  A forward that skips and finds the
-        # value rows of its conditioning state reads nothing of it and does not project it (`null_kv_once`; one 44 us launch per forward
-        # at DiT-XL); a forward that reads it projects it as before, and where the conditional projection is reused (`reuse_cond_kv`)
-        # it projects the entry unless this conditioning state was the last to do so.
-        reads_null = dedup and not (self.null_kv_once and skip and cs.get("vrow") is not None)
-        if need_kv:
-            project_kv(not ride, reads_null)
-            if ride_state["on"]:
-                ops.linear_heads_fold_pair(None, *kv_problem(0))     # block 0's projection: a launch of its own, on the riders' tile kernel
-        elif reads_null and not null_kv_valid():
-            project_null_kv()
-        if skip and cs.get("vrow") is None:
-            # ONCE per conditioning state, behind the broadcast entry's first projection: the rows depend on the null embedding and
-            # the packed to_v weights only, which live exactly as long as `cs` does (`null16` above; repack() drops both) - every
-            # later forward of the loop launches nothing here (and, with `null_kv_once`, does not project the entry either)
-            cs["vrow"] = null_value_rows()
-        if two_streams:
-            # Two HIP streams, one per CFG half (the conditional and the unconditional rows are independent chains of
-            # kernels): every GEMM of this path ends with a write burst that nothing of ITS OWN kernel can overlap
-            # (DESIGN_LOG.md section 4); with the second chain a few kernels behind the first, one chain's burst drains
-            # under the other chain's matrix phase.  Same kernels, same arithmetic per row.
-            main = torch.cuda.current_stream()
-            side = self._side_stream(dev)
-            side.wait_stream(main)                       # embeddings, modulation and the K / V projection come first
-            lag = torch.cuda.Event()
-            for i, w in enumerate(pk["blocks"]):
-                block(i, w, 0, B, hook=(lambda: lag.record(main)) if i == 0 else None)
-                with torch.cuda.stream(side):
-                    if i == 0:
-                        side.wait_event(lag)             # the side chain starts when the main one is three kernels in
-                    block(i, w, B, Be)
-            main.wait_stream(side)
-        elif one_call:
-            # ONE foreign call for the forward's blocks (primx_dit_blocks_fold, ABI 24): the C side issues the launches block() below
-            # would - same entry points, same arguments, same order, bit-identical results - at ~1 us of host time each instead of
-            # ~21 us of Python + ctypes (tools/host_bound_check.py).  The per-block descriptors are built once per planned loop.
-            f, desc = fold_call(ride)
-            ops._dev(h, "h", torch.float32)                 # (the launch-device check of every op: ops._stream)
-            _lib.check(_lib.load().primx_dit_blocks_fold(C.byref(f), desc, ops._stream()), "primx_dit_blocks_fold")
+        r = self._route16(B, N, L, cs["Lk"], D, H, self.depth, Dc, null_half, cs["null16"] is not None,
+                          prow, plan["t"].numel() if prow is not None else None, ops.PROFILE is not None, self.block_probe is not None,
+                          lambda Bkv: self._kv_cached(cs, L, dt, dev, Bkv), cs.get("vrow") is not None, self._fold_ok, ops.fold_pair_fits,
+                          _lib.capabilities())
+        f = _Forward16(self, r, pk, cs, plan, h, mod, B, N, L, dt)
+        f.project_kv()
+        if r.two_streams:
+            f.run_two_streams()
+        elif r.one_call:
+            f.run_one_call()
         else:
-            for i, w in enumerate(pk["blocks"]):
-                block(i, w, 0, Be)
-                if self.block_probe is not None:
-                    rs = h.std(-1)
-                    self.block_probe.append({
-                        "block": i, "folded": fold_uv is not None, "dtype": str(dt).replace("torch.", ""),
-                        "residual_abs_max": float(h.abs().max()), "row_std_min": float(rs.min()), "row_std_median": float(rs.median()),
-                        "row_std_max": float(rs.max()), "row_mean_abs_max": float(h.mean(-1).abs().max()),
-                        "next_operand_abs_max": float(xn.float().abs().max()), "next_operand_finite": bool(torch.isfinite(xn.float()).all())})
-
+            f.run_block_loop()
         # ---- final layer (dit_crossattn.py:74-78)
-        if not (fuse and self.depth):                    # (fused: the last block's fc2 launch has normalised the rows)
-            ops.layernorm_modulate(h, fin_mod[0], fin_mod[1], N, xn, self.LN_EPS)
-        out = ops.linear(xn, pk["w_final"], pk["b_final"])
-        return out.view(Be, N, self.out_channels)
+        if not (r.fuse and self.depth):                  # (fused: the last block's fc2 launch has normalised the rows)
+            ops.layernorm_modulate(h, f.fin_mod[0], f.fin_mod[1], N, f.xn, self.LN_EPS)
+        return ops.linear(f.xn, pk["w_final"], pk["b_final"]).view(Be, N, self.out_channels)
 
     def _forward_fp32(self, x, t, y):
         """The reference with autocast off: every Linear, the attention core, LayerNorm, modulate, GELU and the gated
