@@ -146,6 +146,9 @@ SIGNATURES = {
     "primx_adam_step": [_p, _p, _p, _p, _l, _f, _d, _d, _f, _f, _f, _i, _p],
     "primx_raymarch_backward": [_p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p],
     "primx_material_sample": [_p, _p, _p, _l, _p, _i, _p, _p, _i, _p, _i, _p, _l, _p, _p, _p],
+    "primx_primsdf_query_grad": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "primx_texbake_tangents": [_p, _p, _p, _i, _i, _p, _p],
+    "primx_texbake_normal_texels": [_p, _l, _p, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # An alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI.  Version 21 changed the argument
@@ -154,7 +157,8 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # but what it lacks.  _SINCE: entry point -> the first ABI version that has it (not listed: 21).  _PROBE marks those that joined
 # version 35 without a new number, because they change no existing call: an A/B build of version 35 from before them lacks the
 # symbol, which `load` finds out with hasattr.  A version-24 build ignores the kv_* tail of PrimxDitForwardFold that came with
-# primx_linear_heads_fold_pair (the host then projects K / V itself).
+# primx_linear_heads_fold_pair (the host then projects K / V itself).  The normal map's three entry points joined version 35 the same
+# way but are listed with the number 35: under PRIMX_LIB an absent entry point of 35 is skipped like a probed one.
 _PROBE = 0
 _SINCE: dict = {
     **dict.fromkeys(("primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
@@ -176,6 +180,7 @@ _SINCE: dict = {
     **dict.fromkeys(("primx_mesh_field_query", "primx_mesh_face_areas", "primx_mesh_surface_points", "primx_fps"), 33),  # fit.py
     **dict.fromkeys(("primx_primsdf_query_backward", "primx_adam_step"), 34),                    # differentiable PrimSDF, refine=
     "primx_raymarch_backward": 35,                                                               # the marcher's backward
+    **dict.fromkeys(("primx_primsdf_query_grad", "primx_texbake_tangents", "primx_texbake_normal_texels"), 35),   # the normal map
     **dict.fromkeys(("primx_material_sample",                                                    # a MeshField with a material
                      "primx_attention_ksplit_mode", "primx_attention_ksplit",                    # without them: attention never splits its keys
                      "primx_gemm_toq64_mode",                                                    # without it: to_q under the null skip on the 128-row tile
@@ -230,7 +235,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     bound = set()
     for name, argtypes in SIGNATURES.items():
         since = _SINCE.get(name, 21)
-        if got < since or (since == _PROBE and ab and not hasattr(lib, name)):
+        if got < since or (since in (_PROBE, 35) and ab and not hasattr(lib, name)):
             continue                # an older A/B build: it lacks the entry point (or, before 23, has it with another argument list)
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.argtypes = argtypes

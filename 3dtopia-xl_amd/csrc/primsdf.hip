@@ -21,10 +21,14 @@ namespace {
 
 constexpr int CHUNK = 1024;   // primitives per LDS chunk (16 KB)
 
+// GRAD: also the gradient of channel 0 with respect to the point (primx_primsdf_query_grad; rules in include/primx_hip.h).  The
+// forward's statements are shared, so out has the same bits in both instantiations; the gradient adds six register sums
+// (ga = sum_k [sigma_k grad w_k + w_k grad sigma_k], gw = sum_k grad w_k) and the chosen grid point's offset on the fill path.
+template <bool GRAD>
 __global__ __launch_bounds__(256) void primsdf_query_kernel(const float* __restrict__ pts, const float* __restrict__ srt,
                                                            const float* __restrict__ feat, const float* __restrict__ lin,
-                                                           float* __restrict__ out, int n, int P, int S, int C,
-                                                           int eval_fill) {
+                                                           float* __restrict__ out, float* __restrict__ grad, int n, int P,
+                                                           int S, int C, int eval_fill) {
     __shared__ float4 prim[CHUNK];   // (scale, x, y, z)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
@@ -33,6 +37,7 @@ __global__ __launch_bounds__(256) void primsdf_query_kernel(const float* __restr
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float wsum = 0.f, best = 3.4e38f;
     int best_i = 0;
+    float ga[3] = {0.f, 0.f, 0.f}, gw[3] = {0.f, 0.f, 0.f};
     const int S3 = S * S * S;
     const float half = 0.5f * (float)(S - 1);
     for (int p0 = 0; p0 < P; p0 += CHUNK) {
@@ -71,6 +76,29 @@ __global__ __launch_bounds__(256) void primsdf_query_kernel(const float* __restr
                 const float s = (c00 * (1.f - ty) + c01 * ty) * (1.f - tz) + (c10 * (1.f - ty) + c11 * ty) * tz;
                 acc[c] += w * s;
             }
+            if constexpr (GRAD) {
+                // channel 0 again, with its three cell-local derivatives (the backward's expressions)
+                const float ux = 1.f - tx, uy = 1.f - ty, uz = 1.f - tz;
+                const float v000 = vol[0], v001 = vol[1], v010 = vol[S], v011 = vol[S + 1];
+                const float v100 = vol[S * S], v101 = vol[S * S + 1], v110 = vol[S * S + S], v111 = vol[S * S + S + 1];
+                const float c00 = v000 * ux + v001 * tx, c01 = v010 * ux + v011 * tx;
+                const float c10 = v100 * ux + v101 * tx, c11 = v110 * ux + v111 * tx;
+                const float c0 = c00 * uy + c01 * ty, c1 = c10 * uy + c11 * ty;
+                const float sig = c0 * uz + c1 * tz;
+                const float hs = w * (half / q.x);                              // w_k (S - 1) / (2 s_k)
+                ga[0] += hs * (((v001 - v000) * uy + (v011 - v010) * ty) * uz + ((v101 - v100) * uy + (v111 - v110) * ty) * tz);
+                ga[1] += hs * ((c01 - c00) * uz + (c11 - c10) * tz);
+                ga[2] += hs * (c1 - c0);
+                const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
+                const int j = (ax >= ay && ax >= az) ? 0 : ((ay >= az) ? 1 : 2);   // first of equals, x, y, z order
+                const float dj = j == 0 ? dx : (j == 1 ? dy : dz);
+                const float wj = (dj < 0.f ? 1.f : (dj > 0.f ? -1.f : 0.f)) / as;   // grad w_k = -sign(d_j) / |s| e_j
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    gw[a] += a == j ? wj : 0.f;
+                    ga[a] += a == j ? sig * wj : 0.f;
+                }
+            }
         }
     }
     if (!live) return;
@@ -84,13 +112,18 @@ __global__ __launch_bounds__(256) void primsdf_query_kernel(const float* __restr
         const float px[3] = {x, y, z}, pc[3] = {q.y, q.z, q.w};
         int idx[3];
         float d2 = 0.f;
+        float off[3] = {0.f, 0.f, 0.f};                                         // x - g per axis (GRAD)
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             int bi = 0;
             float bd = 3.4e38f;
             for (int k = 0; k < S; ++k) {
                 const float e = px[a] - (pc[a] + q.x * lin[k]);
-                if (e * e < bd) { bd = e * e; bi = k; }
+                if (e * e < bd) {
+                    bd = e * e;
+                    bi = k;
+                    if constexpr (GRAD) off[a] = e;
+                }
             }
             idx[a] = bi;
             d2 += bd;
@@ -98,6 +131,19 @@ __global__ __launch_bounds__(256) void primsdf_query_kernel(const float* __restr
         const float s = feat[(int64_t)best_i * C * S3 + (idx[2] * S + idx[1]) * S + idx[0]];   // channel 0, [z][y][x]
         const float sgn = (s > 0.f) ? 1.f : ((s < 0.f) ? -1.f : 0.f);
         r[0] = s + sqrtf(d2) * sgn;
+        if constexpr (GRAD) {
+            const float dist = sqrtf(d2);
+            const float k = dist > 0.f ? sgn / dist : 0.f;                      // sign(s) (x - g) / dist; 0 at dist == 0 or s == 0
+            gw[0] = gw[1] = gw[2] = 0.f;
+            ga[0] = k * off[0]; ga[1] = k * off[1]; ga[2] = k * off[2];
+        }
+    }
+    if constexpr (GRAD) {
+        // covered: (ga - o gw) / (W + 1e-6); uncovered: the fill's gradient as it stands (inv multiplies 0 sums without the fill)
+        const bool filled = eval_fill && !(wsum > 0.f);
+        float* go = grad + 3 * (int64_t)i;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) go[a] = filled ? ga[a] : (ga[a] - r[0] * gw[a]) * inv;
     }
     float* o = out + (int64_t)i * C;
     o[0] = r[0];
@@ -112,9 +158,19 @@ extern "C" int primx_primsdf_query(const float* pts, const float* srt, const flo
                                    int n, int P, int S, int C, int eval_fill, void* stream) {
     PRIMX_REQUIRE(pts && srt && feat && lin && out, "primx_primsdf_query: null pointer");
     PRIMX_REQUIRE(n > 0 && P > 0 && S >= 2 && S <= 32 && C >= 1 && C <= 6, "primx_primsdf_query: need n, P > 0, 2 <= S <= 32, 1 <= C <= 6");
-    hipLaunchKernelGGL(primsdf_query_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pts, srt, feat,
-                       lin, out, n, P, S, C, eval_fill);
+    hipLaunchKernelGGL(primsdf_query_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pts, srt, feat,
+                       lin, out, (float*)nullptr, n, P, S, C, eval_fill);
     PRIMX_CHECK_LAUNCH("primx_primsdf_query");
+    return PRIMX_OK;
+}
+
+extern "C" int primx_primsdf_query_grad(const float* pts, const float* srt, const float* feat, const float* lin, float* out,
+                                        float* grad, int n, int P, int S, int C, int eval_fill, void* stream) {
+    PRIMX_REQUIRE(pts && srt && feat && lin && out && grad, "primx_primsdf_query_grad: null pointer");
+    PRIMX_REQUIRE(n > 0 && P > 0 && S >= 2 && S <= 32 && C >= 1 && C <= 6, "primx_primsdf_query_grad: need n, P > 0, 2 <= S <= 32, 1 <= C <= 6");
+    hipLaunchKernelGGL(primsdf_query_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pts, srt, feat,
+                       lin, out, grad, n, P, S, C, eval_fill);
+    PRIMX_CHECK_LAUNCH("primx_primsdf_query_grad");
     return PRIMX_OK;
 }
 

@@ -280,6 +280,104 @@ __global__ __launch_bounds__(THREADS) void tb_compact_kernel(const int* __restri
     }
 }
 
+// ------------------------------------------------------------------ normal map: tangents, texel normals
+
+// label -> (u axis, v axis) of its projection (mesh.py PROJECTION); the projection axis is label >> 1
+__constant__ int PROJ_U[6] = {1, 2, 2, 0, 0, 1};
+
+__device__ __forceinline__ float len3(const float* a) { return sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
+__device__ __forceinline__ float dot3(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// rules T1-T4 of include/primx_hip.h; one thread per face corner, equal values from every corner of a split vertex
+__global__ __launch_bounds__(THREADS) void tb_tangents_kernel(const float* __restrict__ nrm, const int* __restrict__ ft,
+                                                              const int* __restrict__ label, int NUV, int F,
+                                                              float* __restrict__ tangent) {
+    const int t = blockIdx.x * THREADS + threadIdx.x;
+    if (t >= 3 * F) return;
+    const int vtx = ft[t], lab = label[t / 3];
+    if (vtx < 0 || vtx >= NUV || lab < 0 || lab > 5) return;
+    const int a = PROJ_U[lab], c = lab >> 1;
+    const float sigma = (lab & 1) ? -1.f : 1.f;
+    const float N[3] = {nrm[3 * (size_t)vtx], nrm[3 * (size_t)vtx + 1], nrm[3 * (size_t)vtx + 2]};
+    const float m = fmaxf(fabsf(N[0]), fmaxf(fabsf(N[1]), fabsf(N[2])));
+    float d[3] = {0.f, 0.f, 0.f};
+    d[a] = 1.f;
+    if (fabsf(N[c]) > 1e-4f * m) {                                  // T1
+        d[c] = -__fdiv_rn(N[a], N[c]);
+    } else if (m > 0.f) {                                           // T2
+        const float nn = dot3(N, N);
+        const float k = __fdiv_rn(N[a], nn);
+        for (int x = 0; x < 3; ++x) d[x] = d[x] - N[x] * k;
+        if (dot3(d, d) < 1e-8f) {
+            const float sa = N[a] > 0.f ? 1.f : (N[a] < 0.f ? -1.f : 0.f);
+            const float e = N[c] >= 0.f ? -sa : sa;
+            const float k2 = __fdiv_rn(e * N[c], nn);
+            for (int x = 0; x < 3; ++x) d[x] = (x == c ? e : 0.f) - N[x] * k2;
+        }
+    }
+    const float l = len3(d);
+    float* o = tangent + 4 * (size_t)vtx;
+    for (int x = 0; x < 3; ++x) o[x] = l > 0.f ? __fdiv_rn(d[x], l) : (x == a ? 1.f : 0.f);
+    o[3] = sigma * N[c] < 0.f ? 1.f : -1.f;                         // T4
+}
+
+__global__ __launch_bounds__(THREADS) void tb_normal_texels_kernel(const int* __restrict__ texel, long long n,
+                                                                   const int* __restrict__ fid, int W, int HW,
+                                                                   const int* __restrict__ uv, const int* __restrict__ ft,
+                                                                   int NUV, int F, const float* __restrict__ nrm,
+                                                                   const float* __restrict__ tangent,
+                                                                   const float* __restrict__ g, float* __restrict__ nts,
+                                                                   float* __restrict__ attr) {
+    const long long k = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (k >= n) return;
+    float r[3] = {0.f, 0.f, 1.f};
+    const int t = texel[k];
+    const int face = (t >= 0 && t < HW) ? fid[t] : -1;
+    Tri T;
+    if (face >= 0 && face < F && load_tri(uv, ft, NUV, face, T)) {      // load_tri: corners inside [0, NUV), area > 0
+        const int vi[3] = {ft[3 * (size_t)face], ft[3 * (size_t)face + 1], ft[3 * (size_t)face + 2]};
+        const long long x = (long long)FIX * (t % W) + FIX / 2, y = (long long)FIX * (t / W) + FIX / 2;
+        const float ar = (float)T.area;
+        const float l[3] = {__fdiv_rn((float)edge_fn(T.bx, T.by, T.cx, T.cy, x, y), ar),
+                            __fdiv_rn((float)edge_fn(T.cx, T.cy, T.ax, T.ay, x, y), ar),
+                            __fdiv_rn((float)edge_fn(T.ax, T.ay, T.bx, T.by, x, y), ar)};
+        float Ni[3], Tp[3];
+        for (int c = 0; c < 3; ++c) {
+            Ni[c] = (l[0] * nrm[3 * (size_t)vi[0] + c] + l[1] * nrm[3 * (size_t)vi[1] + c]) + l[2] * nrm[3 * (size_t)vi[2] + c];
+            Tp[c] = (l[0] * tangent[4 * (size_t)vi[0] + c] + l[1] * tangent[4 * (size_t)vi[1] + c]) +
+                    l[2] * tangent[4 * (size_t)vi[2] + c];
+        }
+        const float w = tangent[4 * (size_t)vi[0] + 3];
+        const float ln = len3(Ni);
+        if (ln > 0.f) {
+            for (int c = 0; c < 3; ++c) Ni[c] = __fdiv_rn(Ni[c], ln);
+            const float nt = dot3(Ni, Tp);
+            float Ti[3];
+            for (int c = 0; c < 3; ++c) Ti[c] = Tp[c] - Ni[c] * nt;
+            const float lt = len3(Ti);
+            if (lt > 0.f) {
+                for (int c = 0; c < 3; ++c) Ti[c] = __fdiv_rn(Ti[c], lt);
+                const float B[3] = {w * (Ni[1] * Ti[2] - Ni[2] * Ti[1]), w * (Ni[2] * Ti[0] - Ni[0] * Ti[2]),
+                                    w * (Ni[0] * Ti[1] - Ni[1] * Ti[0])};
+                const float gv[3] = {g[3 * k], g[3 * k + 1], g[3 * k + 2]};
+                const float q[3] = {dot3(gv, Ti), dot3(gv, B), dot3(gv, Ni)};
+                const float lq = len3(q);
+                if (lq > 0.f)
+                    for (int c = 0; c < 3; ++c) r[c] = __fdiv_rn(q[c], lq);
+            }
+        }
+    }
+    for (int c = 0; c < 3; ++c) nts[3 * k + c] = r[c];
+    if (attr) {
+        float* o = attr + 6 * k;
+        o[0] = 0.f; o[4] = 0.f; o[5] = 0.f;
+        for (int c = 0; c < 3; ++c) {
+            const float b = rintf(255.f * (0.5f * r[c] + 0.5f));        // byte; the fill's trunc(x * 255) gives it back
+            o[1 + c] = __fdiv_rn(b + 0.5f, 255.f);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ quantize + fill
 
 __device__ __forceinline__ uint8_t quant(float x) {
@@ -607,5 +705,33 @@ extern "C" int primx_texbake_fill(const float* attr, const int* texel, int64_t n
     hipLaunchKernelGGL(tb_fill_kernel, dim3(nblocks(W, TILE), nblocks(H, TILE)), dim3(THREADS), 0, st,
                        (const uint8_t*)bandmap, face_id, (const uint8_t*)img, W, H, radius, albedo, metallic_roughness);
     PRIMX_CHECK_LAUNCH("primx_texbake_fill (fill)");
+    return PRIMX_OK;
+}
+
+extern "C" int primx_texbake_tangents(const float* nrm, const int* ft, const int* label, int NUV, int F, float* tangent,
+                                      void* stream) {
+    if (int s = check_mesh("primx_texbake_tangents", 0, F, NUV)) return s;
+    PRIMX_REQUIRE(4 * (int64_t)NUV < I31, "primx_texbake_tangents: 4 * NUV must be < 2^31 (got NUV = %d)", NUV);
+    if (F == 0) return PRIMX_OK;
+    PRIMX_REQUIRE(nrm && ft && label && tangent, "primx_texbake_tangents: null pointer");
+    PRIMX_REQUIRE(NUV >= 1, "primx_texbake_tangents: faces without vertices (NUV = 0)");
+    hipLaunchKernelGGL(tb_tangents_kernel, dim3(nblocks(3 * (int64_t)F, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, nrm,
+                       ft, label, NUV, F, tangent);
+    PRIMX_CHECK_LAUNCH("primx_texbake_tangents");
+    return PRIMX_OK;
+}
+
+extern "C" int primx_texbake_normal_texels(const int* texel, int64_t n, const int* face_id, int W, int H, const int* uv,
+                                           const int* ft, int NUV, int F, const float* nrm, const float* tangent,
+                                           const float* g, float* nts, float* attr, void* stream) {
+    if (int s = check_atlas("primx_texbake_normal_texels", W, H)) return s;
+    if (int s = check_mesh("primx_texbake_normal_texels", 0, F, NUV)) return s;
+    PRIMX_REQUIRE(4 * (int64_t)NUV < I31, "primx_texbake_normal_texels: 4 * NUV must be < 2^31 (got NUV = %d)", NUV);
+    PRIMX_REQUIRE(n >= 0 && n <= (int64_t)W * H, "primx_texbake_normal_texels: n = %lld is not a count of texels", (long long)n);
+    if (n == 0) return PRIMX_OK;
+    PRIMX_REQUIRE(texel && face_id && uv && ft && nrm && tangent && g && nts, "primx_texbake_normal_texels: null pointer");
+    hipLaunchKernelGGL(tb_normal_texels_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, texel,
+                       (long long)n, face_id, W, W * H, uv, ft, NUV, F, nrm, tangent, g, nts, attr);
+    PRIMX_CHECK_LAUNCH("primx_texbake_normal_texels");
     return PRIMX_OK;
 }

@@ -229,7 +229,8 @@ def primitives_to_texmesh(recon_param_b: torch.Tensor, resolution: int = 256, te
     """recon_param[b] [N, 4 + 6 S^3] -> `mesh.TexturedMesh`: the sample's primitives (as `primitives_to_mesh` builds them)
     through `mesh.extract_texmesh(field, resolution, texture_size, **kw)` - the UV-mapped PBR GLB of inference.py:86-225
     `clean=True` adds the reference's `clean_mesh` step and `decimate=N` its `decimate_mesh` step (`mesh.DECIMATE_TARGET`
-    = 100000 in its configuration) before the bake."""
+    = 100000 in its configuration) before the bake; `normal_map=True` also bakes the field's normals into a tangent-space
+    normal map (TANGENT + normalTexture in the GLB)."""
     from .mesh import extract_texmesh
     from .primsdf import PrimSDF
     if recon_param_b.dim() != 2:

@@ -10,7 +10,8 @@ constructor still refuses `f_sdf` / `geo_fn` / `asset_list`.  `PrimSDF.from_mesh
 
 Like the reference's module in `.train()`, a `PrimSDF(differentiable=True)` in training mode is differentiable in `srt_param`
 and `feat_param`: `primx_primsdf_query_backward` (`query_backward` below) is the backward of the training-mode query.  There is
-no gradient with respect to the points.
+no gradient with respect to the points under autograd; `PrimSDF.query_grad` / `normals` return the analytic gradient of the sdf
+with respect to the points as plain tensors (`primx_primsdf_query_grad`), which the normal-map bake of mesh.py reads.
 """
 from __future__ import annotations
 
@@ -152,6 +153,36 @@ class PrimSDF(nn.Module):
             ops._dev(self._linspace(x.device), "lin", torch.float32), out.data_ptr(), n, srt.shape[0], self.prim_shape,
             self.dim_feat, 0 if self.training else 1, ops._stream()), "primx_primsdf_query")
         return out
+
+    def query_grad(self, x: torch.Tensor):
+        """x: [n, 3] fp32 on the HIP device -> (out [n, dim_feat], grad [n, 3]): `query`'s columns (the same bits, with the fill
+        of uncovered points in eval mode and without it in `.train()`, as `query` chooses) and the analytic gradient of the sdf
+        column with respect to the point (`primx_primsdf_query_grad`, rules in include/primx_hip.h).  The parameters are
+        detached and nothing here is recorded by autograd."""
+        if not x.is_cuda:
+            raise RuntimeError("PrimSDF.query_grad needs HIP device tensors; there is no CPU path")
+        if self.dim_feat != 6 or self.srt_param.shape[0] == 0:
+            raise NotImplementedError("the query kernel covers the 6-channel PrimX payload")
+        x = x.detach().float().contiguous()
+        n = x.shape[0]
+        out = torch.empty(n, self.dim_feat, dtype=torch.float32, device=x.device)
+        grad = torch.empty(n, 3, dtype=torch.float32, device=x.device)
+        if n == 0:
+            return out, grad
+        srt = self.srt_param.detach().float().contiguous()
+        feat = self.feat_param.detach().float().contiguous()
+        _lib.check(_lib.load().primx_primsdf_query_grad(
+            ops._dev(x, "x", torch.float32), ops._dev(srt, "srt", torch.float32), ops._dev(feat, "feat", torch.float32),
+            ops._dev(self._linspace(x.device), "lin", torch.float32), out.data_ptr(), grad.data_ptr(), n, srt.shape[0],
+            self.prim_shape, self.dim_feat, 0 if self.training else 1, ops._stream()), "primx_primsdf_query_grad")
+        return out, grad
+
+    def normals(self, x: torch.Tensor) -> torch.Tensor:
+        """x: [n, 3] -> [n, 3] unit field normals grad / |grad| of `query_grad`, (0, 0, 0) where the gradient is zero.  They point
+        towards higher sdf values, outward, like the lattice normals of `mesh.marching_cubes(return_normals=True)`."""
+        grad = self.query_grad(x)[1]
+        length = grad.norm(dim=1, keepdim=True)
+        return torch.where(length > 0, grad / length.clamp_min(1e-38), torch.zeros_like(grad))
 
     @ops.on_input_device
     def forward(self, x: torch.Tensor):

@@ -665,6 +665,27 @@ int primx_primsdf_query(const float* pts, const float* srt, const float* feat, c
 int primx_primsdf_query_backward(const float* pts, const float* srt, const float* feat, const float* gout, float* gsrt,
                                  float* gfeat, int n, int P, int S, int C, void* stream);
 
+/* The query together with the gradient of its channel 0 (the SDF) with respect to the POINT (added to ABI 35 without a new
+ * number: no existing call changes).  Arguments and domain as primx_primsdf_query, plus grad [n, 3] fp32 (not null).
+ * out [n, C] holds the bits primx_primsdf_query writes for the same arguments: the same kernel body, the same cull, weight,
+ * cell and sample expressions in the same order.  Per point x and covering primitive k (the forward's cull and its w_k > 0
+ * test), with d = x - pos_k, s = scale_k, half = (S - 1) / 2:
+ *   - covered point, W = sum_k w_k, o = sum_k w_k sigma_k / (W + 1e-6), sigma_k = the trilinear sample of channel 0:
+ *       grad o = (sum_k [sigma_k grad w_k + w_k grad sigma_k] - o sum_k grad w_k) / (W + 1e-6)
+ *       grad w_k = -sign(d_j) / |s| e_j, j = the axis of the maximum |d_a|, the first of equals in x, y, z order (the
+ *                  backward's convention); sign(0) = 0;
+ *       grad sigma_k = half / s * (d sigma / d t_x, d sigma / d t_y, d sigma / d t_z), the cell-local derivatives of the
+ *                  trilinear sample inside the forward's own cell min(floor(f), S - 2) clamped at 0 (the backward's b_ka
+ *                  without its weights); a negative scale samples at the signed d / s and weighs as |s|, as the forward;
+ *   - uncovered point, eval_fill != 0: the fill is s + dist sign(s) with s the stored SDF at the chosen grid point g of the
+ *     nearest primitive and dist = ||x - g||, so grad = sign(s) (x - g) / dist; 0 where dist == 0 or s == 0;
+ *   - uncovered point, eval_fill == 0: grad = 0 exactly.
+ * One thread per point, the primitives streamed through LDS in the forward's 1024-primitive chunks, the six gradient sums
+ * in registers: no atomics, bitwise deterministic.  Nothing outside out / grad is written; no workspace, no host
+ * synchronisation. */
+int primx_primsdf_query_grad(const float* pts, const float* srt, const float* feat, const float* lin, float* out, float* grad,
+                             int n, int P, int S, int C, int eval_fill, void* stream);
+
 /* One Adam step over n fp32 elements, in place on param, m, v (torch.optim.Adam without amsgrad and weight decay), every
  * expression as written and uncontracted, division and square root correctly rounded:
  *   m = m + w1 (g - m);  v = v fl(beta2) + (w2 g) g;  param = param - ((lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps)
@@ -751,6 +772,48 @@ int primx_texbake_compact(const int* face_id, int W, int H, const void* ws, int6
 int primx_texbake_fill_workspace(int W, int H, int64_t* bytes);
 int primx_texbake_fill(const float* attr, const int* texel, int64_t n, const int* face_id, int W, int H, int radius,
                        int band, void* ws, int64_t ws_bytes, uint8_t* albedo, uint8_t* metallic_roughness, void* stream);
+
+/* Tangent-space normal map (no counterpart in the reference; glTF 2.0 section 3.9.3 "Normal texture", 3.7.2.1 TANGENT).  Both
+ * entry points were added to ABI 35 without a new number: no existing call changes.  fp32 without FMA contraction, division
+ * and square root correctly rounded.
+ *
+ * primx_texbake_tangents: one TANGENT per split vertex of the atlas.  nrm [NUV, 3] fp32 = the normal N of each split vertex
+ * (any length), ft [F, 3] int32 = the atlas's faces (into the split vertices), label [F] int32 = the faces' projection labels
+ * -> tangent [NUV, 4] fp32 = (unit T, w = +-1).  One thread per face corner; every face that shares a split vertex shares its
+ * chart and so its label, hence every corner of a vertex computes and stores the same four values from the same N: no
+ * accumulation, no atomics, bitwise deterministic.  A split vertex no face names is not written (the caller zeroes tangent);
+ * a corner out of [0, NUV) or a label out of 0..5 stores nothing.  With (a, b) = the label's (u, v) axes, c = label / 2 its
+ * projection axis and sigma = +1 for an even label, -1 for an odd one (e_a x e_b = sigma e_c for all six projections):
+ *   T1  |N_c| > 1e-4 max(|N_x|, |N_y|, |N_z|):  d = e_a - (N_a / N_c) e_c.  This is d pos / d u at constant v on the plane
+ *       through the vertex orthogonal to N (a step e_a in u must be paid for by -N_a / N_c along the axis to stay on it), and
+ *       d . N = 0 whatever the length of N.
+ *   T2  otherwise (the plane contains the projection axis; N == 0 counts):  d = e_a - N (N_a / N . N), Gram-Schmidt of e_a
+ *       against N (d = e_a when N == 0); where that leaves |d|^2 < 1e-8 (N along e_a), d = e_c' - N (e_c' . N / N . N) with
+ *       e_c' = -sign(N_a) e_c for N_c >= 0 and +sign(N_a) e_c for N_c < 0, the limit of T1's direction.
+ *   T3  T = d / |d|.
+ *   T4  w = -1 where sigma N_c >= 0, +1 where sigma N_c < 0.  Derivation: vt has v = 0 at the first image row, so "up the
+ *       image" (+Y of a glTF normal texture, whose +X is right = increasing u) is DEcreasing v, and glTF defines
+ *       bitangent = cross(normal, tangent) * w.  On the vertex's plane d pos / d v at constant u is d_v = e_b - (N_b / N_c) e_c.
+ *       In the (a, b, c) frame d x d_v = (N_a / N_c, N_b / N_c, 1) times the frame's handedness sigma, so
+ *       cross(N, T) . d_v = N . (T x d_v) = sigma |N|^2 / (N_c |d|): cross(N, T) points towards INcreasing v exactly when
+ *       sigma N_c > 0, i.e. when the label agrees with the vertex normal, and then w must be -1 to turn it up the image.
+ *       For a chart whose label matches its faces that is every vertex: w = -1.
+ *
+ * primx_texbake_normal_texels: one thread per covered texel k of primx_texbake_compact's list (texel [n] int32, n <= W H;
+ * face_id, uv, ft as there).  nrm [NUV, 3] and tangent [NUV, 4] per split vertex; g [n, 3] fp32 = the unit field normal at the
+ * texel's point (0 where the field has none).  With the covering face's barycentrics l by primx_texbake_compact's rule
+ * (la = fp32(E_bc) / fp32(area2), ...; sums as (a + b) + c):
+ *   N_i = normalize(sum l N);  T' = sum l T.xyz;  T_i = normalize(T' - N_i (N_i . T'));  B = w cross(N_i, T_i), w = the first
+ *   corner's (it is constant within a face);  n_ts = normalize(g . T_i, g . B, g . N_i) -> nts [n, 3] fp32.
+ * A zero g, a zero sum l N, a zero T' - N_i (N_i . T'), a face without positive snapped area or an index out of range gives
+ * (0, 0, 1).  attr [n, 6] fp32 (may be null) receives the map ready for primx_texbake_fill: columns 1..3 =
+ * (byte + 0.5) / 255 with byte = rint(255 (0.5 n_ts + 0.5)) (ties to even), columns 0, 4, 5 = 0; the fill's
+ * trunc(x * 255) reproduces byte with half a step of margin, and its albedo output is the normal map.  n == 0 launches
+ * nothing. */
+int primx_texbake_tangents(const float* nrm, const int* ft, const int* label, int NUV, int F, float* tangent, void* stream);
+int primx_texbake_normal_texels(const int* texel, int64_t n, const int* face_id, int W, int H, const int* uv, const int* ft,
+                                int NUV, int F, const float* nrm, const float* tangent, const float* g, float* nts,
+                                float* attr, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Mesh cleanup (inference.py:126: clean_mesh(v, f, min_f=8, min_d=5, repair=True, remesh=False), the pymeshlab filters

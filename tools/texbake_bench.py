@@ -5,7 +5,11 @@ texels, the fp32 field query, the quantize + fill, and the PNG / GLB write.  Two
 examples/generate.py poses a random-weight sample (scale 0.05-0.08, centres in [-0.6, 0.6]^3, random payload).  Each
 stage is timed with a device synchronisation around it, median of --reps runs after one warm-up.
 
-    python tools/texbake_bench.py [--reps 5] [--sizes 1024 2048]
+    python tools/texbake_bench.py [--reps 5] [--sizes 1024 2048] [--normal-map]
+
+--normal-map adds the rows of the tangent-space normal map (mesh.bake_normal_map, stage by stage): the field's gradient query
+at the texel points, the tangents, the texel normals, the second fill, the GLB write with the third PNG, and the total of
+`bake_textures(normal_map=True)` next to the plain one.
 """
 import argparse
 import os
@@ -31,7 +35,7 @@ def stage(name, fn, times):
     return out
 
 
-def bake_stages(M, field, mesh, size, times):
+def bake_stages(M, field, mesh, size, times, normal_map=False):
     """mesh.bake_textures, stage by stage (the same calls)."""
     v, f, n = mesh.v, mesh.f, mesh.normals
     nv, nf = v.shape[0], f.shape[0]
@@ -58,6 +62,16 @@ def bake_stages(M, field, mesh, size, times):
     with tempfile.TemporaryDirectory() as d:
         stage("PNG + GLB write", lambda: tm.write_glb(os.path.join(d, "m.glb")), times)
     stage("bake_textures total", lambda: M.bake_textures(field, mesh, size), times)
+    if normal_map:
+        nv_ = n[atlas.vmap].contiguous()
+        g = stage("normal map: gradient query", lambda: M.field_normals(field, pts), times)
+        tan = stage("normal map: tangents", lambda: M.atlas_tangents(atlas, nv_), times)
+        _, nattr = stage("normal map: texel normals", lambda: M.texel_normals(atlas, texel, nv_, tan, g, with_attr=True), times)
+        nmap, _ = stage("normal map: fill", lambda: M.fill_textures(nattr, texel, atlas.face_id), times)
+        tm.tangents, tm.normal_map = tan, nmap
+        with tempfile.TemporaryDirectory() as d:
+            stage("normal map: GLB write with 3 PNGs", lambda: tm.write_glb(os.path.join(d, "m.glb")), times)
+        stage("bake_textures(normal_map=True) total", lambda: M.bake_textures(field, mesh, size, normal_map=True), times)
     return atlas, nc
 
 
@@ -66,6 +80,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", type=int, nargs="+", default=[1024, 2048])
     ap.add_argument("--resolution", type=int, default=256)
+    ap.add_argument("--normal-map", action="store_true", help="also time the stages of the tangent-space normal map")
     a = ap.parse_args()
     __graft_entry__.build()
     from topia_xl_amd import mesh as M
@@ -85,7 +100,7 @@ def main():
                 continue
             for rep in range(a.reps + 1):
                 t = {}
-                atlas, nc = bake_stages(M, field, mesh, size, t)
+                atlas, nc = bake_stages(M, field, mesh, size, t, a.normal_map)
                 if rep:
                     for k, x in t.items():
                         times.setdefault(k, []).extend(x)
