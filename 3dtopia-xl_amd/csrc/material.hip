@@ -24,11 +24,10 @@
 
 namespace {
 
-constexpr int THREADS = 256;
+#include "mesh_common.h"
+
 constexpr int MAX_EXTENT = 65536;        // W and H at most: 2 W fits an int with room, float(W) is exact
 constexpr float X_LIMIT = 1073741824.0f; // |texel coordinate| is clamped to 2^30 before it becomes an int
-
-inline int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
 
 struct Tex {
     int64_t off;
@@ -174,10 +173,7 @@ extern "C" int primx_material_sample(const float* uv, const float* vattr, const 
     PRIMX_REQUIRE(T == 0 || tex_desc, "%s: null texture table with T = %d", name, T);
     PRIMX_REQUIRE(n_texels == 0 || (texels && ((uintptr_t)texels & 3) == 0), "%s: the texel blob must be 4-byte aligned", name);
     PRIMX_REQUIRE(n == 0 || (uv && face && out), "%s: null pointer", name);
-    if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) {
-        primx_set_error("%s: hipMemsetAsync failed", name);
-        return PRIMX_ELAUNCH;
-    }
+    PRIMX_TRY(zero(status, sizeof(int), st, name));
     hipLaunchKernelGGL(mat_check_kernel, dim3(nblocks((int64_t)F + M + T, THREADS)), dim3(THREADS), 0, st, face_material, F, mat_tex,
                        M, tex_desc, T, n_texels, status);
     PRIMX_CHECK_LAUNCH(name);
@@ -187,11 +183,7 @@ extern "C" int primx_material_sample(const float* uv, const float* vattr, const 
         PRIMX_CHECK_LAUNCH(name);
     }
     int flag = 0;
-    if (hipMemcpyAsync(&flag, status, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        primx_set_error("%s: reading back the index check failed", name);
-        return PRIMX_ELAUNCH;
-    }
+    PRIMX_TRY(readback(&flag, status, sizeof(flag), st, name));
     PRIMX_REQUIRE(!(flag & 1), "%s: a face lies outside [0, F)", name);
     PRIMX_REQUIRE(!(flag & 2), "%s: a material index lies outside [0, M)", name);
     PRIMX_REQUIRE(!(flag & 4), "%s: a texture index lies outside [-1, T)", name);

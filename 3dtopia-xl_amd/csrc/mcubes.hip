@@ -22,10 +22,7 @@
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int ROUNDS = 4;
-constexpr int PTS = THREADS * ROUNDS;   // points per block
-constexpr int SCAN_THREADS = 1024;
+#include "mesh_common.h"
 
 struct Dims {
     int nx, ny, nz;
@@ -44,33 +41,9 @@ __device__ __forceinline__ unsigned corner_off(const Dims& d, int c) {
     return (c & 1) * d.nynz + ((c >> 1) & 1) * (unsigned)d.nz + ((c >> 2) & 1);
 }
 
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// Exclusive prefix of c (0..7) over the block's 256 threads in thread order; `total` = the block's sum.  Every thread
-// of the block calls it.
-__device__ __forceinline__ int block_prefix(int c, int* s_wave, int& total) {
-    const unsigned long long b0 = __ballot(c & 1), b1 = __ballot(c & 2), b2 = __ballot(c & 4);
-    const int pre = lanes_below(b0) + 2 * lanes_below(b1) + 4 * lanes_below(b2);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) s_wave[wave] = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) {
-        off += (w < wave) ? s_wave[w] : 0;
-        tot += s_wave[w];
-    }
-    __syncthreads();
-    total = tot;
-    return off + pre;
-}
-
 __global__ __launch_bounds__(THREADS) void mc_classify_kernel(const float* __restrict__ vol, Dims d, float iso,
                                                               unsigned* __restrict__ words, long long* __restrict__ bsum) {
     __shared__ int8_t s_ntri[256];
-    __shared__ int s_red[2][THREADS / 64];
     s_ntri[threadIdx.x] = MC_NTRI[threadIdx.x];
     __syncthreads();
     int nv = 0, nt = 0;
@@ -94,48 +67,7 @@ __global__ __launch_bounds__(THREADS) void mc_classify_kernel(const float* __res
         nv += __popc(vb);
         nt += t;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_down(nv, o);
-        nt += __shfl_down(nt, o);
-    }
-    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = nv; s_red[1][threadIdx.x >> 6] = nt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long a = 0, b = 0;
-        for (int w = 0; w < THREADS / 64; ++w) { a += s_red[0][w]; b += s_red[1][w]; }
-        bsum[2 * (size_t)blockIdx.x] = a;
-        bsum[2 * (size_t)blockIdx.x + 1] = b;
-    }
-}
-
-// One workgroup: thread t owns the contiguous run [t * per, (t + 1) * per) of the block sums.
-__global__ __launch_bounds__(SCAN_THREADS) void mc_scan_kernel(long long* __restrict__ bsum, int nblk,
-                                                               long long* __restrict__ totals) {
-    __shared__ long long s[2][SCAN_THREADS];
-    const int per = (nblk + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int lo = min(nblk, (int)threadIdx.x * per), hi = min(nblk, lo + per);
-    long long a = 0, b = 0;
-    for (int q = lo; q < hi; ++q) { a += bsum[2 * (size_t)q]; b += bsum[2 * (size_t)q + 1]; }
-    s[0][threadIdx.x] = a;
-    s[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int o = 1; o < SCAN_THREADS; o <<= 1) {   // inclusive Hillis-Steele scan
-        const long long xa = threadIdx.x >= o ? s[0][threadIdx.x - o] : 0, xb = threadIdx.x >= o ? s[1][threadIdx.x - o] : 0;
-        __syncthreads();
-        s[0][threadIdx.x] += xa;
-        s[1][threadIdx.x] += xb;
-        __syncthreads();
-    }
-    a = s[0][threadIdx.x] - a;
-    b = s[1][threadIdx.x] - b;
-    for (int q = lo; q < hi; ++q) {
-        const long long va = bsum[2 * (size_t)q], vb = bsum[2 * (size_t)q + 1];
-        bsum[2 * (size_t)q] = a;
-        bsum[2 * (size_t)q + 1] = b;
-        a += va;
-        b += vb;
-    }
-    if (threadIdx.x == SCAN_THREADS - 1) { totals[0] = s[0][threadIdx.x]; totals[1] = s[1][threadIdx.x]; }
+    block_sums(nv, nt, bsum);
 }
 
 // d value / d axis at point p (index units): central differences inside, one-sided at the borders (np.gradient, edge_order 1)
@@ -156,7 +88,7 @@ __global__ __launch_bounds__(THREADS) void mc_vertices_kernel(const float* __res
         const bool live = p < d.n;
         const unsigned vb = live ? (words[p] >> 8) & 7u : 0u;
         int tot;
-        const int pre = block_prefix(__popc(vb), s_wave, tot);
+        const int pre = block_prefix3(__popc(vb), s_wave, tot);
         long long o = run + pre;
         run += tot;
         if (vb == 0) continue;
@@ -210,7 +142,7 @@ __global__ __launch_bounds__(THREADS) void mc_triangles_kernel(Dims d, const uns
         const unsigned w = p < d.n ? words[p] : 0u;
         const int nt = (int)((w >> 11) & 7u);
         int tot;
-        const int pre = block_prefix(nt, s_wave, tot);
+        const int pre = block_prefix3(nt, s_wave, tot);
         int* out = tris + 3 * (run + pre);
         run += tot;
         const int8_t* row = s_tri + 16 * (w & 255u);
@@ -254,10 +186,6 @@ __global__ __launch_bounds__(THREADS) void noise_filter_kernel(const float* __re
 // ------------------------------------------------------------------ host side
 namespace {
 
-constexpr size_t ALIGN = 256;
-
-size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-
 struct Layout {
     size_t words, voff, bsum, total;
     int nblk;
@@ -266,11 +194,12 @@ struct Layout {
 Layout layout(int nx, int ny, int nz) {
     const size_t n = (size_t)nx * ny * nz;
     Layout l;
-    l.nblk = (int)((n + PTS - 1) / PTS);
-    l.words = 0;
-    l.voff = align_up(n * 4);
-    l.bsum = l.voff + align_up(n * 4);
-    l.total = l.bsum + align_up((size_t)l.nblk * 16);
+    Arena a;
+    l.nblk = nblocks(n, PTS);
+    l.words = a.take(n * 4);
+    l.voff = a.take(n * 4);
+    l.bsum = a.take((size_t)l.nblk * 16);
+    l.total = a.total;
     return l;
 }
 
@@ -293,7 +222,7 @@ Dims dims(int nx, int ny, int nz) {
 
 extern "C" int primx_mcubes_workspace(int nx, int ny, int nz, int64_t* bytes) {
     PRIMX_REQUIRE(bytes, "primx_mcubes_workspace: null pointer");
-    if (int s = check_dims("primx_mcubes_workspace", nx, ny, nz)) return s;
+    PRIMX_TRY(check_dims("primx_mcubes_workspace", nx, ny, nz));
     *bytes = (int64_t)layout(nx, ny, nz).total;
     return PRIMX_OK;
 }
@@ -301,7 +230,7 @@ extern "C" int primx_mcubes_workspace(int nx, int ny, int nz, int64_t* bytes) {
 extern "C" int primx_mcubes_count(const float* vol, int nx, int ny, int nz, float iso, void* ws, int64_t ws_bytes,
                                   int64_t* totals, void* stream) {
     PRIMX_REQUIRE(vol && ws && totals, "primx_mcubes_count: null pointer");
-    if (int s = check_dims("primx_mcubes_count", nx, ny, nz)) return s;
+    PRIMX_TRY(check_dims("primx_mcubes_count", nx, ny, nz));
     const Layout l = layout(nx, ny, nz);
     PRIMX_REQUIRE(ws_bytes >= (int64_t)l.total, "primx_mcubes_count: workspace of %lld bytes, need %lld",
                   (long long)ws_bytes, (long long)l.total);
@@ -309,16 +238,13 @@ extern "C" int primx_mcubes_count(const float* vol, int nx, int ny, int nz, floa
     hipLaunchKernelGGL(mc_classify_kernel, dim3(l.nblk), dim3(THREADS), 0, (hipStream_t)stream, vol, dims(nx, ny, nz), iso,
                        (unsigned*)(w + l.words), (long long*)(w + l.bsum));
     PRIMX_CHECK_LAUNCH("primx_mcubes_count (classify)");
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, (long long*)(w + l.bsum), l.nblk,
-                       (long long*)totals);
-    PRIMX_CHECK_LAUNCH("primx_mcubes_count (scan)");
-    return PRIMX_OK;
+    return scan_blocks((long long*)(w + l.bsum), l.nblk, (long long*)totals, (hipStream_t)stream, "primx_mcubes_count (scan)");
 }
 
 extern "C" int primx_mcubes_emit(const float* vol, int nx, int ny, int nz, float iso, const void* ws, int64_t ws_bytes,
                                  int64_t nverts, int64_t ntris, float* verts, float* normals, int* tris, void* stream) {
     PRIMX_REQUIRE(vol && ws, "primx_mcubes_emit: null pointer");
-    if (int s = check_dims("primx_mcubes_emit", nx, ny, nz)) return s;
+    PRIMX_TRY(check_dims("primx_mcubes_emit", nx, ny, nz));
     const Layout l = layout(nx, ny, nz);
     PRIMX_REQUIRE(ws_bytes >= (int64_t)l.total, "primx_mcubes_emit: workspace of %lld bytes, need %lld",
                   (long long)ws_bytes, (long long)l.total);
@@ -341,7 +267,7 @@ extern "C" int primx_mcubes_emit(const float* vol, int nx, int ny, int nz, float
 extern "C" int primx_noise_filter(const float* srt, int P, uint8_t* keep, void* stream) {
     PRIMX_REQUIRE(srt && keep, "primx_noise_filter: null pointer");
     PRIMX_REQUIRE(P > 0, "primx_noise_filter: need P > 0 (got %d)", P);
-    hipLaunchKernelGGL(noise_filter_kernel, dim3((P + THREADS - 1) / THREADS), dim3(THREADS), 0, (hipStream_t)stream, srt, P,
+    hipLaunchKernelGGL(noise_filter_kernel, dim3(nblocks(P, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, srt, P,
                        keep);
     PRIMX_CHECK_LAUNCH("primx_noise_filter");
     return PRIMX_OK;

@@ -30,12 +30,11 @@
 
 namespace {
 
-#include "block_scan.h"
+#include "mesh_common.h"
 
 constexpr int GRID_CAP = 128;            // grid cells per axis at most
 constexpr int ROUND_BATCH = 8;           // merge rounds between two reads of the change flags
 constexpr int UND = 0, CEN = 1, CAPT = 2, FIN = 3, NONE = 4;   // merge states (NONE: unreferenced)
-constexpr int REGIONS = 8;               // int regions of M entries in the workspace
 
 __device__ __forceinline__ int ord_enc(float x) {
     const int i = __float_as_int(x);
@@ -46,81 +45,6 @@ __device__ __host__ __forceinline__ float ord_dec(int i) {
     float x;
     memcpy(&x, &b, 4);
     return x;
-}
-
-__device__ __forceinline__ int wave_min(int x) {
-    for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o));
-    return x;
-}
-__device__ __forceinline__ int wave_max(int x) {
-    for (int o = 32; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o));
-    return x;
-}
-__device__ __forceinline__ int wave_sum(int x) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
-// Exclusive prefix of an int over the block's 256 threads in thread order; `total` = the block's sum.
-__device__ __forceinline__ int block_excl(int x, int* s_wave, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(inc, o);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) {
-        off += (w < wave) ? s_wave[w] : 0;
-        tot += s_wave[w];
-    }
-    __syncthreads();
-    total = tot;
-    return off + inc - x;
-}
-
-__global__ __launch_bounds__(THREADS) void mc_fill_kernel(int* __restrict__ a, int n, int value) {
-    const int t = blockIdx.x * THREADS + threadIdx.x;
-    if (t < n) a[t] = value;
-}
-
-// ------------------------------------------------------------------ generic: flags -> ranks, ints -> offsets
-
-__global__ __launch_bounds__(THREADS) void mc_sum_kernel(const int* __restrict__ x, int n, int as_flag,
-                                                         long long* __restrict__ bsum) {
-    int c = 0;
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int t = blockIdx.x * PTS + r * THREADS + threadIdx.x;
-        if (t < n) c += as_flag ? (x[t] != 0 ? 1 : 0) : x[t];
-    }
-    block_sums(c, 0, bsum);
-}
-
-// as_flag: rank[t] = position of t among the set flags (-1 when clear); else out[t] = exclusive prefix sum (and out2)
-__global__ __launch_bounds__(THREADS) void mc_place_kernel(const int* __restrict__ x, int n, int as_flag,
-                                                           const long long* __restrict__ boff, int* __restrict__ out,
-                                                           int* __restrict__ out2) {
-    __shared__ int s_wave[THREADS / 64];
-    long long run = boff[2 * (size_t)blockIdx.x];
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int t = blockIdx.x * PTS + r * THREADS + threadIdx.x;
-        const int val = t < n ? x[t] : 0;
-        int tot;
-        if (as_flag) {
-            const int pre = block_prefix(val != 0, s_wave, tot);
-            if (t < n) out[t] = val != 0 ? (int)(run + pre) : -1;
-        } else {
-            const int pre = block_excl(val, s_wave, tot);
-            if (t < n) {
-                out[t] = (int)(run + pre);
-                if (out2) out2[t] = (int)(run + pre);
-            }
-        }
-        run += tot;
-    }
 }
 
 // ------------------------------------------------------------------ merge (R0-R2)
@@ -500,45 +424,12 @@ __global__ __launch_bounds__(THREADS) void mc_corner_out_kernel(const int* __res
 // ------------------------------------------------------------------ host side
 namespace {
 
-constexpr size_t ALIGN = 256;
-constexpr int64_t I31 = (int64_t)1 << 31;
 constexpr int64_t NCELLS = (int64_t)GRID_CAP * GRID_CAP * GRID_CAP;
 
-size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
+// 8 int regions of M entries, 4 pairs of totals, the change flags of a batch of rounds
+using Ws = MeshWs<8, 4, ROUND_BATCH>;
 
-// REGIONS int arrays of M entries, the block sums of M items, 4 pairs of totals, the change flags, 8 ints of boxes
-struct Layout {
-    int64_t M;
-    size_t region[REGIONS], bsum, tot, flags, small, total;
-};
-
-Layout layout(int V, int F) {
-    Layout l;
-    l.M = std::max<int64_t>({(int64_t)V, 3 * (int64_t)F, NCELLS + 1, 1});
-    size_t o = 0;
-    for (int r = 0; r < REGIONS; ++r) { l.region[r] = o; o += align_up((size_t)l.M * 4); }
-    l.bsum = o;
-    o += align_up((size_t)nblocks(l.M, PTS) * 16);
-    l.tot = o;
-    o += align_up(8 * 8);
-    l.flags = o;
-    o += align_up(ROUND_BATCH * 4);
-    l.small = o;
-    o += align_up(8 * 4);
-    l.total = o;
-    return l;
-}
-
-struct Ws {
-    Layout l;
-    char* w;
-    int* R(int r) const { return (int*)(w + l.region[r]); }
-    long long* bsum() const { return (long long*)(w + l.bsum); }
-    long long* tot(int k) const { return (long long*)(w + l.tot) + 2 * k; }
-    int* flags() const { return (int*)(w + l.flags); }
-    int* small() const { return (int*)(w + l.small); }
-};
+int64_t items(int V, int F) { return std::max<int64_t>({(int64_t)V, 3 * (int64_t)F, NCELLS + 1, 1}); }
 
 int check_sizes(const char* name, int V, int F) {
     PRIMX_REQUIRE(V >= 0 && F >= 0, "%s: need V, F >= 0 (got %d, %d)", name, V, F);
@@ -547,64 +438,14 @@ int check_sizes(const char* name, int V, int F) {
     return PRIMX_OK;
 }
 
-int check_ws(const char* name, int V, int F, const void* ws, int64_t ws_bytes, Ws& out) {
-    PRIMX_REQUIRE(ws, "%s: null pointer", name);
-    out.l = layout(V, F);
-    out.w = (char*)ws;
-    PRIMX_REQUIRE(ws_bytes >= (int64_t)out.l.total, "%s: workspace of %lld bytes, need %lld", name, (long long)ws_bytes,
-                  (long long)out.l.total);
-    return PRIMX_OK;
-}
-
-int fill(int* a, int64_t n, int value, hipStream_t st, const char* name) {
-    if (n <= 0) return PRIMX_OK;
-    hipLaunchKernelGGL(mc_fill_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, a, (int)n, value);
-    PRIMX_CHECK_LAUNCH(name);
-    return PRIMX_OK;
-}
-
-// flags x [n] -> rank [n] (position among the set flags, -1 when clear), or ints -> exclusive offsets; totals in tot[0]
-int scan(const int* x, int n, bool as_flag, int* out, int* out2, const Ws& ws, long long* tot, hipStream_t st,
-         const char* name) {
-    if (n == 0) {
-        if (hipMemsetAsync(tot, 0, 16, st) != hipSuccess) {
-            primx_set_error("%s: hipMemsetAsync failed", name);
-            return PRIMX_ELAUNCH;
-        }
-        return PRIMX_OK;
-    }
-    const int nblk = nblocks(n, PTS);
-    hipLaunchKernelGGL(mc_sum_kernel, dim3(nblk), dim3(THREADS), 0, st, x, n, (int)as_flag, ws.bsum());
-    PRIMX_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(tb_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, ws.bsum(), nblk, tot);
-    PRIMX_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(mc_place_kernel, dim3(nblk), dim3(THREADS), 0, st, x, n, (int)as_flag,
-                       (const long long*)ws.bsum(), out, out2);
-    PRIMX_CHECK_LAUNCH(name);
-    return PRIMX_OK;
-}
-
-int readback(void* host, const void* dev, size_t bytes, hipStream_t st, const char* name) {
-    if (hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        primx_set_error("%s: reading back the counts failed", name);
-        return PRIMX_ELAUNCH;
-    }
-    return PRIMX_OK;
-}
-
 float host_dec(int i) { return ord_dec(i); }
 
 }  // namespace
 
-#define MC_TRY(x)                  \
-    do {                           \
-        if (int s__ = (x)) return s__; \
-    } while (0)
-
 extern "C" int primx_meshclean_workspace(int V, int F, int64_t* bytes) {
     PRIMX_REQUIRE(bytes, "primx_meshclean_workspace: null pointer");
-    MC_TRY(check_sizes("primx_meshclean_workspace", V, F));
-    *bytes = (int64_t)layout(V, F).total;
+    PRIMX_TRY(check_sizes("primx_meshclean_workspace", V, F));
+    *bytes = (int64_t)Ws(items(V, F)).total;
     return PRIMX_OK;
 }
 
@@ -612,30 +453,30 @@ extern "C" int primx_meshclean_merge(const float* v, const int* f, int V, int F,
                                      int* centre, int64_t* rounds, float* radius, void* stream) {
     const char* name = "primx_meshclean_merge";
     PRIMX_REQUIRE(rounds && radius, "%s: null pointer", name);
-    MC_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_sizes(name, V, F));
     PRIMX_REQUIRE(v_pct >= 0.0 && std::isfinite(v_pct), "%s: need a finite v_pct >= 0 (got %g)", name, v_pct);
     *rounds = 0;
     *radius = 0.f;
     if (V == 0) return PRIMX_OK;
     PRIMX_REQUIRE(v && centre && (F == 0 || f), "%s: null pointer", name);
     Ws w;
-    MC_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     int *ref = w.R(0), *st0 = w.R(1), *st1 = w.R(2), *captor = w.R(3), *cellof = w.R(4), *cursor = w.R(5), *start = w.R(6),
         *sorted = w.R(7), *bb = w.small();
-    MC_TRY(fill(ref, V, 0, st, name));
+    PRIMX_TRY(fill(ref, V, 0, st, name));
     if (F > 0) {
         hipLaunchKernelGGL(mc_ref_kernel, dim3(nblocks(3 * (int64_t)F, THREADS)), dim3(THREADS), 0, st, f, F, V, ref);
         PRIMX_CHECK_LAUNCH(name);
     }
     bool merged = false;
     if (v_pct > 0.0 && F > 0) {
-        MC_TRY(fill(bb, 3, INT_MAX, st, name));
-        MC_TRY(fill(bb + 3, 3, INT_MIN, st, name));
+        PRIMX_TRY(fill(bb, 3, INT_MAX, st, name));
+        PRIMX_TRY(fill(bb + 3, 3, INT_MIN, st, name));
         hipLaunchKernelGGL(mc_bbox_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, st, v, (const int*)ref, V, bb);
         PRIMX_CHECK_LAUNCH(name);
         int h[6];
-        MC_TRY(readback(h, bb, sizeof(h), st, name));
+        PRIMX_TRY(readback(h, bb, sizeof(h), st, name));
         merged = h[0] != INT_MAX;
         if (merged) {
             double ext[3], emax = 0.0;
@@ -657,11 +498,11 @@ extern "C" int primx_meshclean_merge(const float* v, const int* f, int V, int F,
                 g.d[a] = std::max(1, g.d[a]);
                 ncell *= g.d[a];
             }
-            MC_TRY(fill(cursor, ncell + 1, 0, st, name));
+            PRIMX_TRY(fill(cursor, ncell + 1, 0, st, name));
             hipLaunchKernelGGL(mc_cell_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, st, v, (const int*)ref, V, g,
                                cellof, cursor);
             PRIMX_CHECK_LAUNCH(name);
-            MC_TRY(scan(cursor, (int)ncell + 1, false, start, cursor, w, w.tot(0), st, name));
+            PRIMX_TRY(scan(cursor, (int)ncell + 1, false, start, cursor, w.bsum(), w.tot(0), st, name));
             hipLaunchKernelGGL(mc_scatter_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, st, (const int*)cellof, V,
                                cursor, sorted, st0, st1);
             PRIMX_CHECK_LAUNCH(name);
@@ -671,10 +512,7 @@ extern "C" int primx_meshclean_merge(const float* v, const int* f, int V, int F,
             while (done_rounds < 0) {
                 PRIMX_REQUIRE(issued <= 2 * (int64_t)V + ROUND_BATCH, "%s: no convergence after %lld rounds", name,
                               (long long)issued);
-                if (hipMemsetAsync(w.flags(), 0, ROUND_BATCH * sizeof(int), st) != hipSuccess) {
-                    primx_set_error("%s: hipMemsetAsync failed", name);
-                    return PRIMX_ELAUNCH;
-                }
+                PRIMX_TRY(zero(w.flags(), ROUND_BATCH * sizeof(int), st, name));
                 for (int q = 0; q < ROUND_BATCH; ++q) {
                     hipLaunchKernelGGL(mc_round_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, st, v,
                                        (const int*)cellof, (const int*)start, (const int*)sorted, V, g, r2,
@@ -683,7 +521,7 @@ extern "C" int primx_meshclean_merge(const float* v, const int* f, int V, int F,
                     cur ^= 1;
                 }
                 int hf[ROUND_BATCH];
-                MC_TRY(readback(hf, w.flags(), sizeof(hf), st, name));
+                PRIMX_TRY(readback(hf, w.flags(), sizeof(hf), st, name));
                 for (int q = 0; q < ROUND_BATCH && done_rounds < 0; ++q)
                     if (hf[q] == 0) done_rounds = issued + q;   // a round without change: every later one too
                 issued += ROUND_BATCH;
@@ -702,27 +540,27 @@ extern "C" int primx_meshclean_faces(const float* v, const int* fr, const int* t
                                      int* out_f, int64_t* n_out, void* stream) {
     const char* name = "primx_meshclean_faces";
     PRIMX_REQUIRE(n_out, "%s: null pointer", name);
-    MC_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_sizes(name, V, F));
     *n_out = 0;
     if (F == 0) return PRIMX_OK;
     PRIMX_REQUIRE(v && fr && tid && out_f, "%s: null pointer", name);
     PRIMX_REQUIRE(V >= 1, "%s: faces without vertices (V = 0)", name);
     Ws w;
-    MC_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     int *minface = w.R(0), *keep = w.R(1), *rank = w.R(2);
-    MC_TRY(fill(minface, F, INT_MAX, st, name));
+    PRIMX_TRY(fill(minface, F, INT_MAX, st, name));
     hipLaunchKernelGGL(mc_face_min_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, fr, tid, V, F, minface);
     PRIMX_CHECK_LAUNCH(name);
     hipLaunchKernelGGL(mc_face_keep_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, v, fr, tid,
                        (const int*)minface, V, F, keep);
     PRIMX_CHECK_LAUNCH(name);
-    MC_TRY(scan(keep, F, true, rank, nullptr, w, w.tot(0), st, name));
+    PRIMX_TRY(scan(keep, F, true, rank, nullptr, w.bsum(), w.tot(0), st, name));
     hipLaunchKernelGGL(mc_gather_rows_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, fr, (const int*)rank, F, 3,
                        out_f);
     PRIMX_CHECK_LAUNCH(name);
     long long h[2];
-    MC_TRY(readback(h, w.tot(0), sizeof(h), st, name));
+    PRIMX_TRY(readback(h, w.tot(0), sizeof(h), st, name));
     *n_out = h[0];
     return PRIMX_OK;
 }
@@ -733,7 +571,7 @@ extern "C" int primx_meshclean_components(const float* v, const int* f, const in
                                           int64_t* counts, void* stream) {
     const char* name = "primx_meshclean_components";
     PRIMX_REQUIRE(counts, "%s: null pointer", name);
-    MC_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_sizes(name, V, F));
     PRIMX_REQUIRE(min_f >= 0 && min_d >= 0.0 && std::isfinite(min_d), "%s: need min_f >= 0 and a finite min_d >= 0 "
                   "(got %d, %g)", name, min_f, min_d);
     PRIMX_REQUIRE(n_comp >= 0 && n_comp <= F && U >= 0 && U <= 3 * (int64_t)F,
@@ -743,7 +581,7 @@ extern "C" int primx_meshclean_components(const float* v, const int* f, const in
     PRIMX_REQUIRE(v && f && node && comp && out_f && out_node && cand_key, "%s: null pointer", name);
     PRIMX_REQUIRE(V >= 1 && n_comp >= 1 && U >= 1, "%s: faces without vertices, components or edges", name);
     Ws w;
-    MC_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     // R0 cnt, R1-R2 boxes (6 n_comp <= 2 M), R3 drop, R4 face rank, R5 edge counts, R6 candidates, R7 scratch
     int *cnt = w.R(0), *bb = w.R(1), *drop = w.R(3), *frank = w.R(4), *ecnt = w.R(5), *cand = w.R(6), *scratch = w.R(7),
@@ -760,12 +598,12 @@ extern "C" int primx_meshclean_components(const float* v, const int* f, const in
     hipLaunchKernelGGL(mc_comp_decide_kernel, dim3(nblocks(n_comp, THREADS)), dim3(THREADS), 0, st, (const int*)cnt,
                        (const int*)bb, (const int*)gbb, n_comp, min_f, min_d, drop);
     PRIMX_CHECK_LAUNCH(name);
-    MC_TRY(scan(drop, n_comp, true, scratch, nullptr, w, w.tot(1), st, name));
+    PRIMX_TRY(scan(drop, n_comp, true, scratch, nullptr, w.bsum(), w.tot(1), st, name));
     int* alive = cnt;   // the counts are read: reuse the region for the face flags
     hipLaunchKernelGGL(mc_face_alive_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, comp, (const int*)drop, F,
                        n_comp, alive);
     PRIMX_CHECK_LAUNCH(name);
-    MC_TRY(scan(alive, F, true, frank, nullptr, w, w.tot(0), st, name));
+    PRIMX_TRY(scan(alive, F, true, frank, nullptr, w.bsum(), w.tot(0), st, name));
     hipLaunchKernelGGL(mc_gather_rows_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, f, (const int*)frank, F, 3,
                        out_f);
     PRIMX_CHECK_LAUNCH(name);
@@ -773,23 +611,22 @@ extern "C" int primx_meshclean_components(const float* v, const int* f, const in
                        out_node);
     PRIMX_CHECK_LAUNCH(name);
     if (repair) {
-        MC_TRY(fill(ecnt, U, 0, st, name));
+        PRIMX_TRY(fill(ecnt, U, 0, st, name));
         hipLaunchKernelGGL(mc_edge_count_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, node, (const int*)alive, F,
                            U, ecnt);
         PRIMX_CHECK_LAUNCH(name);
         hipLaunchKernelGGL(mc_cand_flag_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, node, (const int*)alive,
                            (const int*)ecnt, F, U, cand);
         PRIMX_CHECK_LAUNCH(name);
-        MC_TRY(scan(cand, F, true, scratch, nullptr, w, w.tot(2), st, name));
+        PRIMX_TRY(scan(cand, F, true, scratch, nullptr, w.bsum(), w.tot(2), st, name));
         hipLaunchKernelGGL(mc_cand_key_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, v, f, (const int*)scratch,
                            (const int*)frank, V, F, (long long*)cand_key);
         PRIMX_CHECK_LAUNCH(name);
-    } else if (hipMemsetAsync(w.tot(2), 0, 16, st) != hipSuccess) {
-        primx_set_error("%s: hipMemsetAsync failed", name);
-        return PRIMX_ELAUNCH;
+    } else {
+        PRIMX_TRY(zero(w.tot(2), 16, st, name));
     }
     long long h[6];
-    MC_TRY(readback(h, w.tot(0), sizeof(h), st, name));
+    PRIMX_TRY(readback(h, w.tot(0), sizeof(h), st, name));
     counts[0] = h[0];   // faces kept
     counts[1] = h[2];   // components removed
     counts[2] = h[4];   // R6 candidates
@@ -800,7 +637,7 @@ extern "C" int primx_meshclean_edges(const int* f, const int* node, int F, int U
                                      void* ws, int64_t ws_bytes, int* out_f, int64_t* n_out, void* stream) {
     const char* name = "primx_meshclean_edges";
     PRIMX_REQUIRE(n_out, "%s: null pointer", name);
-    MC_TRY(check_sizes(name, 0, F));
+    PRIMX_TRY(check_sizes(name, 0, F));
     PRIMX_REQUIRE(U >= 0 && U <= 3 * (int64_t)F && n_cand >= 0 && n_cand <= F,
                   "%s: need 0 <= U <= 3 F and 0 <= n_cand <= F (got %d, %lld, F = %d)", name, U, (long long)n_cand, F);
     *n_out = 0;
@@ -808,11 +645,11 @@ extern "C" int primx_meshclean_edges(const int* f, const int* node, int F, int U
     PRIMX_REQUIRE(f && node && out_f && (n_cand == 0 || cand_key), "%s: null pointer", name);
     PRIMX_REQUIRE(U >= 1, "%s: faces without edges (U = 0)", name);
     Ws w;
-    MC_TRY(check_ws(name, 0, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(0, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     int *ecnt = w.R(0), *keep = w.R(1), *rank = w.R(2);
-    MC_TRY(fill(ecnt, U, 0, st, name));
-    MC_TRY(fill(keep, F, 1, st, name));
+    PRIMX_TRY(fill(ecnt, U, 0, st, name));
+    PRIMX_TRY(fill(keep, F, 1, st, name));
     if (n_cand > 0) {
         hipLaunchKernelGGL(mc_edge_count_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, node, nullptr, F, U, ecnt);
         PRIMX_CHECK_LAUNCH(name);
@@ -820,12 +657,12 @@ extern "C" int primx_meshclean_edges(const int* f, const int* node, int F, int U
                            (long long)n_cand, F, U, ecnt, keep);
         PRIMX_CHECK_LAUNCH(name);
     }
-    MC_TRY(scan(keep, F, true, rank, nullptr, w, w.tot(0), st, name));
+    PRIMX_TRY(scan(keep, F, true, rank, nullptr, w.bsum(), w.tot(0), st, name));
     hipLaunchKernelGGL(mc_gather_rows_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, f, (const int*)rank, F, 3,
                        out_f);
     PRIMX_CHECK_LAUNCH(name);
     long long h[2];
-    MC_TRY(readback(h, w.tot(0), sizeof(h), st, name));
+    PRIMX_TRY(readback(h, w.tot(0), sizeof(h), st, name));
     *n_out = h[0];
     return PRIMX_OK;
 }
@@ -834,21 +671,21 @@ extern "C" int primx_meshclean_fans(const int* f, const int* fan, int V, int F, 
                                     int* out_f, int64_t* vmap, int64_t* counts, void* stream) {
     const char* name = "primx_meshclean_fans";
     PRIMX_REQUIRE(counts, "%s: null pointer", name);
-    MC_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_sizes(name, V, F));
     PRIMX_REQUIRE(n_fans >= 0 && n_fans <= 3 * (int64_t)F, "%s: need 0 <= n_fans <= 3 F (got %d, F = %d)", name, n_fans, F);
     counts[0] = counts[1] = 0;
     if (F == 0) return PRIMX_OK;
     PRIMX_REQUIRE(f && out_f && vmap, "%s: null pointer", name);
     PRIMX_REQUIRE(V >= 1 && (!fan || n_fans >= 1), "%s: faces without vertices or fans", name);
     Ws w;
-    MC_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     const int n = 3 * F;
     int *nfans = w.R(0), *lowc = w.R(1), *ref = w.R(2), *firstc = w.R(3), *newid = w.R(4), *srank = w.R(5), *split = w.R(6);
-    MC_TRY(fill(nfans, V, 0, st, name));
-    MC_TRY(fill(lowc, V, INT_MAX, st, name));
-    MC_TRY(fill(ref, V, 0, st, name));
-    MC_TRY(fill(firstc, n_fans, INT_MAX, st, name));
+    PRIMX_TRY(fill(nfans, V, 0, st, name));
+    PRIMX_TRY(fill(lowc, V, INT_MAX, st, name));
+    PRIMX_TRY(fill(ref, V, 0, st, name));
+    PRIMX_TRY(fill(firstc, n_fans, INT_MAX, st, name));
     hipLaunchKernelGGL(mc_corner_a_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, f, fan, n, V, n_fans, ref, lowc,
                        firstc);
     PRIMX_CHECK_LAUNCH(name);
@@ -860,8 +697,8 @@ extern "C" int primx_meshclean_fans(const int* f, const int* fan, int V, int F, 
     hipLaunchKernelGGL(mc_split_flag_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, f, n, V, (const int*)lowc,
                        (const int*)nfans, split);
     PRIMX_CHECK_LAUNCH(name);
-    MC_TRY(scan(split, n, true, srank, nullptr, w, w.tot(1), st, name));
-    MC_TRY(scan(ref, V, true, newid, nullptr, w, w.tot(0), st, name));
+    PRIMX_TRY(scan(split, n, true, srank, nullptr, w.bsum(), w.tot(1), st, name));
+    PRIMX_TRY(scan(ref, V, true, newid, nullptr, w.bsum(), w.tot(0), st, name));
     hipLaunchKernelGGL(mc_vmap_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, st, (const int*)newid, V,
                        (long long*)vmap);
     PRIMX_CHECK_LAUNCH(name);
@@ -870,7 +707,7 @@ extern "C" int primx_meshclean_fans(const int* f, const int* fan, int V, int F, 
                        (const long long*)w.tot(0), out_f, (long long*)vmap);
     PRIMX_CHECK_LAUNCH(name);
     long long h[4];
-    MC_TRY(readback(h, w.tot(0), sizeof(h), st, name));
+    PRIMX_TRY(readback(h, w.tot(0), sizeof(h), st, name));
     counts[0] = h[0];   // referenced input vertices
     counts[1] = h[2];   // split vertices
     return PRIMX_OK;

@@ -26,72 +26,10 @@
 
 namespace {
 
-#include "block_scan.h"
+#include "mesh_common.h"
 
-constexpr int REGIONS = 4;               // int regions of M entries in the workspace
 constexpr int CLS_BOUNDARY = 1, CLS_LOCKED = 2;
 constexpr long long KEY_NONE = LLONG_MAX;
-
-__device__ __forceinline__ int wave_sum_i(int x) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
-// Exclusive prefix of an int over the block's 256 threads in thread order; `total` = the block's sum.
-__device__ __forceinline__ int block_excl(int x, int* s_wave, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(inc, o);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) {
-        off += (w < wave) ? s_wave[w] : 0;
-        tot += s_wave[w];
-    }
-    __syncthreads();
-    total = tot;
-    return off + inc - x;
-}
-
-__global__ __launch_bounds__(THREADS) void md_fill_kernel(int* __restrict__ a, int n, int value) {
-    const int t = blockIdx.x * THREADS + threadIdx.x;
-    if (t < n) a[t] = value;
-}
-
-__global__ __launch_bounds__(THREADS) void md_sum_kernel(const int* __restrict__ x, int n, int as_flag,
-                                                         long long* __restrict__ bsum) {
-    int c = 0;
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int t = blockIdx.x * PTS + r * THREADS + threadIdx.x;
-        if (t < n) c += as_flag ? (x[t] != 0 ? 1 : 0) : x[t];
-    }
-    block_sums(c, 0, bsum);
-}
-
-// as_flag: out[t] = position of t among the set flags (-1 when clear); else out[t] = exclusive prefix sum
-__global__ __launch_bounds__(THREADS) void md_place_kernel(const int* __restrict__ x, int n, int as_flag,
-                                                           const long long* __restrict__ boff, int* __restrict__ out) {
-    __shared__ int s_wave[THREADS / 64];
-    long long run = boff[2 * (size_t)blockIdx.x];
-    for (int r = 0; r < ROUNDS; ++r) {
-        const int t = blockIdx.x * PTS + r * THREADS + threadIdx.x;
-        const int val = t < n ? x[t] : 0;
-        int tot;
-        if (as_flag) {
-            const int pre = block_prefix(val != 0, s_wave, tot);
-            if (t < n) out[t] = val != 0 ? (int)(run + pre) : -1;
-        } else {
-            const int pre = block_excl(val, s_wave, tot);
-            if (t < n) out[t] = (int)(run + pre);
-        }
-        run += tot;
-    }
-}
 
 // ------------------------------------------------------------------ small float64 helpers (the order is the rule's)
 
@@ -452,7 +390,7 @@ __global__ __launch_bounds__(THREADS) void md_collapse_kernel(Fans m, int* __res
                                                               int* __restrict__ n_collapsed) {
     const int i = blockIdx.x * THREADS + threadIdx.x;
     const bool go = i < K && sel[i] && (cand[i] & 0xffffffffLL) < m.U && m.F - before[i] > target;
-    const int n = wave_sum_i(go ? 1 : 0);
+    const int n = wave_sum(go ? 1 : 0);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(n_collapsed, n);
     if (!go) return;
     const long long e = cand[i] & 0xffffffffLL;
@@ -538,41 +476,10 @@ __global__ __launch_bounds__(THREADS) void md_normal_kernel(const float* __restr
 // ------------------------------------------------------------------ host side
 namespace {
 
-constexpr size_t ALIGN = 256;
-constexpr int64_t I31 = (int64_t)1 << 31;
+// 4 int regions of M entries, 2 pairs of totals, no change flags; small() holds the collapse counter
+using Ws = MeshWs<4, 2, 0>;
 
-size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
-
-// REGIONS int arrays of M entries, the block sums of M items, 2 pairs of totals, one counter
-struct Layout {
-    int64_t M;
-    size_t region[REGIONS], bsum, tot, small, total;
-};
-
-Layout layout(int V, int F) {
-    Layout l;
-    l.M = std::max<int64_t>(std::max<int64_t>(V, 3 * (int64_t)F), 1);
-    size_t o = 0;
-    for (int r = 0; r < REGIONS; ++r) { l.region[r] = o; o += align_up((size_t)l.M * 4); }
-    l.bsum = o;
-    o += align_up((size_t)nblocks(l.M, PTS) * 16);
-    l.tot = o;
-    o += align_up(4 * 8);
-    l.small = o;
-    o += align_up(8 * 4);
-    l.total = o;
-    return l;
-}
-
-struct Ws {
-    Layout l;
-    char* w;
-    int* R(int r) const { return (int*)(w + l.region[r]); }
-    long long* bsum() const { return (long long*)(w + l.bsum); }
-    long long* tot(int k) const { return (long long*)(w + l.tot) + 2 * k; }
-    int* small() const { return (int*)(w + l.small); }
-};
+int64_t items(int V, int F) { return std::max<int64_t>({(int64_t)V, 3 * (int64_t)F, 1}); }
 
 int check_sizes(const char* name, int V, int F) {
     PRIMX_REQUIRE(V >= 0 && F >= 0, "%s: need V, F >= 0 (got %d, %d)", name, V, F);
@@ -586,75 +493,26 @@ int check_edges(const char* name, int F, int U) {
     return PRIMX_OK;
 }
 
-int check_ws(const char* name, int V, int F, const void* ws, int64_t ws_bytes, Ws& out) {
-    PRIMX_REQUIRE(ws, "%s: null pointer", name);
-    out.l = layout(V, F);
-    out.w = (char*)ws;
-    PRIMX_REQUIRE(ws_bytes >= (int64_t)out.l.total, "%s: workspace of %lld bytes, need %lld", name, (long long)ws_bytes,
-                  (long long)out.l.total);
-    return PRIMX_OK;
-}
-
-int fill(int* a, int64_t n, int value, hipStream_t st, const char* name) {
-    if (n <= 0) return PRIMX_OK;
-    hipLaunchKernelGGL(md_fill_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, a, (int)n, value);
-    PRIMX_CHECK_LAUNCH(name);
-    return PRIMX_OK;
-}
-
-// flags x [n] -> out [n] (position among the set flags, -1 when clear), or ints -> exclusive offsets; totals in tot[0]
-int scan(const int* x, int n, bool as_flag, int* out, const Ws& ws, long long* tot, hipStream_t st, const char* name) {
-    if (n == 0) {
-        if (hipMemsetAsync(tot, 0, 16, st) != hipSuccess) {
-            primx_set_error("%s: hipMemsetAsync failed", name);
-            return PRIMX_ELAUNCH;
-        }
-        return PRIMX_OK;
-    }
-    const int nblk = nblocks(n, PTS);
-    hipLaunchKernelGGL(md_sum_kernel, dim3(nblk), dim3(THREADS), 0, st, x, n, (int)as_flag, ws.bsum());
-    PRIMX_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(tb_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, ws.bsum(), nblk, tot);
-    PRIMX_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(md_place_kernel, dim3(nblk), dim3(THREADS), 0, st, x, n, (int)as_flag, (const long long*)ws.bsum(),
-                       out);
-    PRIMX_CHECK_LAUNCH(name);
-    return PRIMX_OK;
-}
-
-int readback(void* host, const void* dev, size_t bytes, hipStream_t st, const char* name) {
-    if (hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        primx_set_error("%s: reading back the counts failed", name);
-        return PRIMX_ELAUNCH;
-    }
-    return PRIMX_OK;
-}
-
 }  // namespace
-
-#define MD_TRY(x)                      \
-    do {                               \
-        if (int s__ = (x)) return s__; \
-    } while (0)
 
 extern "C" int primx_meshdecim_workspace(int V, int F, int64_t* bytes) {
     PRIMX_REQUIRE(bytes, "primx_meshdecim_workspace: null pointer");
-    MD_TRY(check_sizes("primx_meshdecim_workspace", V, F));
-    *bytes = (int64_t)layout(V, F).total;
+    PRIMX_TRY(check_sizes("primx_meshdecim_workspace", V, F));
+    *bytes = (int64_t)Ws(items(V, F)).total;
     return PRIMX_OK;
 }
 
 extern "C" int primx_meshdecim_edges(const int* f, const int* node, const int* sv, int V, int F, int U, int* ecnt, int* vcls,
                                      int* first, int* last, void* stream) {
     const char* name = "primx_meshdecim_edges";
-    MD_TRY(check_sizes(name, V, F));
-    MD_TRY(check_edges(name, F, U));
+    PRIMX_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_edges(name, F, U));
     if (F == 0) return PRIMX_OK;
     PRIMX_REQUIRE(f && node && sv && ecnt && vcls && first && last, "%s: null pointer", name);
     PRIMX_REQUIRE(V >= 1 && U >= 1, "%s: faces without vertices or edges", name);
     hipStream_t st = (hipStream_t)stream;
     const int n = 3 * F, nb = nblocks(n, THREADS);
-    MD_TRY(fill(ecnt, U, 0, st, name));
+    PRIMX_TRY(fill(ecnt, U, 0, st, name));
     hipLaunchKernelGGL(md_corner_init_kernel, dim3(nb), dim3(THREADS), 0, st, f, n, V, vcls);
     PRIMX_CHECK_LAUNCH(name);
     hipLaunchKernelGGL(md_edge_count_kernel, dim3(nb), dim3(THREADS), 0, st, node, n, U, ecnt);
@@ -670,8 +528,8 @@ extern "C" int primx_meshdecim_quadrics(const float* v, const int* f, const int*
                                         const int* last, const int* ecnt, int V, int F, int U, double* p, double* Q,
                                         void* stream) {
     const char* name = "primx_meshdecim_quadrics";
-    MD_TRY(check_sizes(name, V, F));
-    MD_TRY(check_edges(name, F, U));
+    PRIMX_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_edges(name, F, U));
     if (V == 0) return PRIMX_OK;
     PRIMX_REQUIRE(v && first && last && p && Q && (F == 0 || (f && node && order && ecnt)), "%s: null pointer", name);
     hipLaunchKernelGGL(md_quadric_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, v, f, node, order,
@@ -684,7 +542,7 @@ extern "C" int primx_meshdecim_costs(const double* p, const double* Q, const int
                                      int V, int U, int optimalplacement, double* x, double* cost, int64_t* key, int* valid,
                                      void* stream) {
     const char* name = "primx_meshdecim_costs";
-    MD_TRY(check_sizes(name, V, 0));
+    PRIMX_TRY(check_sizes(name, V, 0));
     PRIMX_REQUIRE(U >= 0 && 3 * (int64_t)U < I31, "%s: need 0 <= 3 U < 2^31 (got U = %d)", name, U);
     if (U == 0) return PRIMX_OK;
     PRIMX_REQUIRE(p && Q && ukeys && ecnt && vcls && x && cost && key && valid, "%s: null pointer", name);
@@ -700,8 +558,8 @@ extern "C" int primx_meshdecim_select(const double* p, const int* f, const int* 
                                       const double* x, const int64_t* cand, int V, int F, int U, int K, int64_t* m1, int* ok,
                                       int* sel, void* stream) {
     const char* name = "primx_meshdecim_select";
-    MD_TRY(check_sizes(name, V, F));
-    MD_TRY(check_edges(name, F, U));
+    PRIMX_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_edges(name, F, U));
     PRIMX_REQUIRE(K >= 0 && K <= U, "%s: need 0 <= K <= U (got K = %d, U = %d)", name, K, U);
     if (K == 0) return PRIMX_OK;
     PRIMX_REQUIRE(p && f && node && order && first && last && ukeys && ecnt && valid && x && cand && m1 && ok && sel,
@@ -727,8 +585,8 @@ extern "C" int primx_meshdecim_collapse(double* p, double* Q, int* f, const int*
                                         int* out_f, int64_t* counts, void* stream) {
     const char* name = "primx_meshdecim_collapse";
     PRIMX_REQUIRE(counts, "%s: null pointer", name);
-    MD_TRY(check_sizes(name, V, F));
-    MD_TRY(check_edges(name, F, U));
+    PRIMX_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_edges(name, F, U));
     PRIMX_REQUIRE(K >= 0 && K <= U && target >= 0, "%s: need 0 <= K <= U and target >= 0 (got K = %d, U = %d, target = %d)", name,
                   K, U, target);
     counts[0] = 0;
@@ -737,30 +595,30 @@ extern "C" int primx_meshdecim_collapse(double* p, double* Q, int* f, const int*
     PRIMX_REQUIRE(p && Q && f && order && first && last && ukeys && ecnt && x && out_f && (K == 0 || (cand && sel)),
                   "%s: null pointer", name);
     Ws w;
-    MD_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     int *weight = w.R(0), *before = w.R(1), *alive = w.R(2), *rank = w.R(3), *n_collapsed = w.small();
-    MD_TRY(fill(alive, F, 1, st, name));
-    MD_TRY(fill(n_collapsed, 1, 0, st, name));
+    PRIMX_TRY(fill(alive, F, 1, st, name));
+    PRIMX_TRY(fill(n_collapsed, 1, 0, st, name));
     if (K > 0) {
         hipLaunchKernelGGL(md_weight_kernel, dim3(nblocks(K, THREADS)), dim3(THREADS), 0, st, (const long long*)cand, sel, ecnt, K,
                            U, weight);
         PRIMX_CHECK_LAUNCH(name);
-        MD_TRY(scan(weight, K, false, before, w, w.tot(1), st, name));
+        PRIMX_TRY(scan(weight, K, false, before, nullptr, w.bsum(), w.tot(1), st, name));
         const Fans m{f, nullptr, order, first, last, V, F, U};
         hipLaunchKernelGGL(md_collapse_kernel, dim3(nblocks(K, THREADS)), dim3(THREADS), 0, st, m, f, p, Q,
                            (const long long*)ukeys, x, (const long long*)cand, sel, (const int*)before, K, target, alive,
                            n_collapsed);
         PRIMX_CHECK_LAUNCH(name);
     }
-    MD_TRY(scan(alive, F, true, rank, w, w.tot(0), st, name));
+    PRIMX_TRY(scan(alive, F, true, rank, nullptr, w.bsum(), w.tot(0), st, name));
     hipLaunchKernelGGL(md_gather_rows_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, (const int*)f, (const int*)rank, F,
                        out_f);
     PRIMX_CHECK_LAUNCH(name);
     long long h[2];
     int hc = 0;
-    MD_TRY(readback(h, w.tot(0), sizeof(h), st, name));
-    MD_TRY(readback(&hc, n_collapsed, sizeof(hc), st, name));
+    PRIMX_TRY(readback(h, w.tot(0), sizeof(h), st, name));
+    PRIMX_TRY(readback(&hc, n_collapsed, sizeof(hc), st, name));
     counts[0] = hc;     // collapses of the round
     counts[1] = h[0];   // live faces after it
     return PRIMX_OK;
@@ -770,27 +628,27 @@ extern "C" int primx_meshdecim_finish(const double* p, const int* f, int V, int 
                                       int* out_f, int64_t* vmap, int64_t* n_out, void* stream) {
     const char* name = "primx_meshdecim_finish";
     PRIMX_REQUIRE(n_out, "%s: null pointer", name);
-    MD_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_sizes(name, V, F));
     *n_out = 0;
     if (F == 0) return PRIMX_OK;
     PRIMX_REQUIRE(V >= 1, "%s: faces without vertices (V = 0)", name);
     PRIMX_REQUIRE(p && f && out_v && out_f && vmap, "%s: null pointer", name);
     Ws w;
-    MD_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     int *ref = w.R(0), *newid = w.R(1);
     const int n = 3 * F;
-    MD_TRY(fill(ref, V, 0, st, name));
+    PRIMX_TRY(fill(ref, V, 0, st, name));
     hipLaunchKernelGGL(md_ref_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, f, n, V, ref);
     PRIMX_CHECK_LAUNCH(name);
-    MD_TRY(scan(ref, V, true, newid, w, w.tot(0), st, name));
+    PRIMX_TRY(scan(ref, V, true, newid, nullptr, w.bsum(), w.tot(0), st, name));
     hipLaunchKernelGGL(md_vertex_out_kernel, dim3(nblocks(V, THREADS)), dim3(THREADS), 0, st, p, (const int*)newid, V, out_v,
                        (long long*)vmap);
     PRIMX_CHECK_LAUNCH(name);
     hipLaunchKernelGGL(md_face_out_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, f, (const int*)newid, n, V, out_f);
     PRIMX_CHECK_LAUNCH(name);
     long long h[2];
-    MD_TRY(readback(h, w.tot(0), sizeof(h), st, name));
+    PRIMX_TRY(readback(h, w.tot(0), sizeof(h), st, name));
     *n_out = h[0];
     return PRIMX_OK;
 }
@@ -798,18 +656,18 @@ extern "C" int primx_meshdecim_finish(const double* p, const int* f, int V, int 
 extern "C" int primx_meshdecim_normals(const float* v, const int* f, const int* sv, const int* order, int V, int F, void* ws,
                                        int64_t ws_bytes, float* normals, void* stream) {
     const char* name = "primx_meshdecim_normals";
-    MD_TRY(check_sizes(name, V, F));
+    PRIMX_TRY(check_sizes(name, V, F));
     if (V == 0) {
         PRIMX_REQUIRE(F == 0, "%s: faces without vertices (V = 0)", name);
         return PRIMX_OK;
     }
     PRIMX_REQUIRE(v && normals && (F == 0 || (f && sv && order)), "%s: null pointer", name);
     Ws w;
-    MD_TRY(check_ws(name, V, F, ws, ws_bytes, w));
+    PRIMX_TRY(check_ws(name, items(V, F), ws, ws_bytes, w));
     hipStream_t st = (hipStream_t)stream;
     int *first = w.R(0), *last = w.R(1);
-    MD_TRY(fill(first, V, 0, st, name));
-    MD_TRY(fill(last, V, 0, st, name));
+    PRIMX_TRY(fill(first, V, 0, st, name));
+    PRIMX_TRY(fill(last, V, 0, st, name));
     if (F > 0) {
         hipLaunchKernelGGL(md_ranges_kernel, dim3(nblocks(3 * (int64_t)F, THREADS)), dim3(THREADS), 0, st, sv, 3 * F, V, first,
                            last);

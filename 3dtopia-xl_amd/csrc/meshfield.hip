@@ -23,13 +23,12 @@
 
 namespace {
 
-constexpr int THREADS = 256;
+#include "mesh_common.h"
+
 constexpr int MF_CHUNK = 256;            // triangle records per LDS chunk (16 KiB)
 constexpr int FPS_MAXB = 256;            // blocks of an fps launch at most (= partial argmaxes per parity)
 constexpr int FPS_PER_BLOCK = 1024;      // candidates per block at least
 constexpr int64_t WS_HEAD = 64;          // bytes in front of the records: the index-check flag
-
-inline int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return (ax * bx + ay * by) + az * bz;
@@ -302,15 +301,6 @@ __global__ __launch_bounds__(THREADS) void fps_nn_kernel(const float* __restrict
     if (k < K) nn[k] = K > 1 ? sqrtf(best) : 0.0f;
 }
 
-int read_flag(const int* status, hipStream_t st, const char* name, int* flag) {
-    if (hipMemcpyAsync(flag, status, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        primx_set_error("%s: reading back the index check failed", name);
-        return PRIMX_ELAUNCH;
-    }
-    return PRIMX_OK;
-}
-
 int check_mesh(const char* name, const void* v, const void* f, int V, int F) {
     PRIMX_REQUIRE(v && f, "%s: null pointer", name);
     PRIMX_REQUIRE(V >= 1 && F >= 1, "%s: V and F must be at least 1 (got %d, %d)", name, V, F);
@@ -320,17 +310,12 @@ int check_mesh(const char* name, const void* v, const void* f, int V, int F) {
 
 }  // namespace
 
-#define MF_TRY(x)                      \
-    do {                               \
-        if (int s__ = (x)) return s__; \
-    } while (0)
-
 extern "C" int primx_mesh_field_query(const float* pts, int64_t n, const float* v, const int* f, int V, int F,
                                       const float* attr, int C, void* ws, int64_t ws_bytes, float* dist, int* face, float* wn,
                                       float* out_attr, void* stream) {
     const char* name = "primx_mesh_field_query";
     hipStream_t st = (hipStream_t)stream;
-    MF_TRY(check_mesh(name, v, f, V, F));
+    PRIMX_TRY(check_mesh(name, v, f, V, F));
     PRIMX_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX * THREADS, "%s: n out of range", name);
     PRIMX_REQUIRE(C >= 0 && C <= 16, "%s: C must lie in 0 .. 16 (got %d)", name, C);
     PRIMX_REQUIRE(C == 0 || attr, "%s: null attribute pointer with C = %d", name, C);
@@ -339,14 +324,11 @@ extern "C" int primx_mesh_field_query(const float* pts, int64_t n, const float* 
     PRIMX_REQUIRE(n == 0 || (pts && dist && face && wn && (C == 0 || out_attr)), "%s: null pointer", name);
     int* status = (int*)ws;
     float4* recs = (float4*)((char*)ws + WS_HEAD);
-    if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) {
-        primx_set_error("%s: hipMemsetAsync failed", name);
-        return PRIMX_ELAUNCH;
-    }
+    PRIMX_TRY(zero(status, sizeof(int), st, name));
     hipLaunchKernelGGL(mf_prep_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, v, f, V, F, recs, status);
     PRIMX_CHECK_LAUNCH(name);
     int flag = 0;
-    MF_TRY(read_flag(status, st, name, &flag));
+    PRIMX_TRY(readback(&flag, status, sizeof(flag), st, name));
     PRIMX_REQUIRE(flag == 0, "%s: a face index lies outside [0, V)", name);
     if (n == 0) return PRIMX_OK;
     hipLaunchKernelGGL(mf_query_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, pts, n, (const float4*)recs, F, f, attr,
@@ -358,16 +340,13 @@ extern "C" int primx_mesh_field_query(const float* pts, int64_t n, const float* 
 extern "C" int primx_mesh_face_areas(const float* v, const int* f, int V, int F, double* area, int* status, void* stream) {
     const char* name = "primx_mesh_face_areas";
     hipStream_t st = (hipStream_t)stream;
-    MF_TRY(check_mesh(name, v, f, V, F));
+    PRIMX_TRY(check_mesh(name, v, f, V, F));
     PRIMX_REQUIRE(area && status, "%s: null pointer", name);
-    if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) {
-        primx_set_error("%s: hipMemsetAsync failed", name);
-        return PRIMX_ELAUNCH;
-    }
+    PRIMX_TRY(zero(status, sizeof(int), st, name));
     hipLaunchKernelGGL(mf_area_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, v, f, V, F, area, status);
     PRIMX_CHECK_LAUNCH(name);
     int flag = 0;
-    MF_TRY(read_flag(status, st, name, &flag));
+    PRIMX_TRY(readback(&flag, status, sizeof(flag), st, name));
     PRIMX_REQUIRE(flag == 0, "%s: a face index lies outside [0, V)", name);
     return PRIMX_OK;
 }
@@ -376,19 +355,16 @@ extern "C" int primx_mesh_surface_points(const float* v, const int* f, int V, in
                                          float* pts, int* face, int* status, void* stream) {
     const char* name = "primx_mesh_surface_points";
     hipStream_t st = (hipStream_t)stream;
-    MF_TRY(check_mesh(name, v, f, V, F));
+    PRIMX_TRY(check_mesh(name, v, f, V, F));
     PRIMX_REQUIRE(cdf && status, "%s: null pointer", name);
     PRIMX_REQUIRE(N >= 0 && N <= (int64_t)INT32_MAX * THREADS, "%s: N out of range", name);
     if (N == 0) return PRIMX_OK;
     PRIMX_REQUIRE(u && pts && face, "%s: null pointer", name);
-    if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) {
-        primx_set_error("%s: hipMemsetAsync failed", name);
-        return PRIMX_ELAUNCH;
-    }
+    PRIMX_TRY(zero(status, sizeof(int), st, name));
     hipLaunchKernelGGL(mf_points_kernel, dim3(nblocks(N, THREADS)), dim3(THREADS), 0, st, v, f, V, F, cdf, u, N, pts, face, status);
     PRIMX_CHECK_LAUNCH(name);
     int flag = 0;
-    MF_TRY(read_flag(status, st, name, &flag));
+    PRIMX_TRY(readback(&flag, status, sizeof(flag), st, name));
     PRIMX_REQUIRE(flag == 0, "%s: a face index lies outside [0, V)", name);
     return PRIMX_OK;
 }

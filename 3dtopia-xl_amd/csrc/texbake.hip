@@ -28,7 +28,7 @@
 
 namespace {
 
-#include "block_scan.h"
+#include "mesh_common.h"
 
 constexpr int ROUND_BATCH = 4;          // union-find rounds between two reads of the change flags
 constexpr int MAX_ROUNDS = 512;
@@ -470,12 +470,6 @@ __global__ __launch_bounds__(THREADS) void tb_fill_kernel(const uint8_t* __restr
 // ------------------------------------------------------------------ host side
 namespace {
 
-constexpr size_t ALIGN = 256;
-constexpr int64_t I31 = (int64_t)1 << 31;
-
-size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-int nblocks(int64_t n, int per) { return (int)((n + per - 1) / per); }
-
 struct CcLayout {
     size_t minface, p0, p1, p2, rank, bsum, flags, tot, total;
     int nblk;
@@ -483,16 +477,17 @@ struct CcLayout {
 
 CcLayout cc_layout(int F, int U) {
     CcLayout l;
+    Arena a;
     l.nblk = nblocks(F, PTS);
-    l.minface = 0;
-    l.p0 = align_up((size_t)U * 4);
-    l.p1 = l.p0 + align_up((size_t)F * 4);
-    l.p2 = l.p1 + align_up((size_t)F * 4);
-    l.rank = l.p2 + align_up((size_t)F * 4);
-    l.bsum = l.rank + align_up((size_t)F * 4);
-    l.flags = l.bsum + align_up((size_t)l.nblk * 16);
-    l.tot = l.flags + align_up(ROUND_BATCH * 4);
-    l.total = l.tot + align_up(16);
+    l.minface = a.take((size_t)U * 4);
+    l.p0 = a.take((size_t)F * 4);
+    l.p1 = a.take((size_t)F * 4);
+    l.p2 = a.take((size_t)F * 4);
+    l.rank = a.take((size_t)F * 4);
+    l.bsum = a.take((size_t)l.nblk * 16);
+    l.flags = a.take(ROUND_BATCH * 4);
+    l.tot = a.take(16);
+    l.total = a.total;
     return l;
 }
 
@@ -510,9 +505,10 @@ struct RasterLayout {
 
 RasterLayout raster_layout(int W, int H) {
     RasterLayout l;
+    Arena a;
     l.nblk = nblocks((int64_t)W * H, PTS);
-    l.bsum = 0;
-    l.total = align_up((size_t)l.nblk * 16);
+    l.bsum = a.take((size_t)l.nblk * 16);
+    l.total = a.total;
     return l;
 }
 
@@ -520,6 +516,19 @@ int check_atlas(const char* name, int W, int H) {
     PRIMX_REQUIRE(W >= 1 && W <= MAX_SIZE && H >= 1 && H <= MAX_SIZE, "%s: W, H must be in [1, %d] (got %d x %d)", name,
                   MAX_SIZE, W, H);
     return PRIMX_OK;
+}
+
+struct FillLayout {
+    size_t img, band, total;
+};
+
+FillLayout fill_layout(int W, int H) {
+    FillLayout l;
+    Arena a;
+    l.img = a.take((size_t)W * H * 8);
+    l.band = a.take((size_t)W * H);
+    l.total = a.total;
+    return l;
 }
 
 int check_mesh(const char* name, int V, int F, int NUV) {
@@ -546,7 +555,7 @@ extern "C" int primx_texbake_labels(const float* v, const float* n, const int* f
 
 extern "C" int primx_texbake_components_workspace(int F, int U, int64_t* bytes) {
     PRIMX_REQUIRE(bytes, "primx_texbake_components_workspace: null pointer");
-    if (int s = check_cc("primx_texbake_components_workspace", F, U)) return s;
+    PRIMX_TRY(check_cc("primx_texbake_components_workspace", F, U));
     *bytes = (int64_t)cc_layout(F, U).total;
     return PRIMX_OK;
 }
@@ -554,7 +563,7 @@ extern "C" int primx_texbake_components_workspace(int F, int U, int64_t* bytes) 
 extern "C" int primx_texbake_components(const int* node, int F, int U, void* ws, int64_t ws_bytes, int* comp,
                                         int64_t* n_comp, void* stream) {
     PRIMX_REQUIRE(n_comp, "primx_texbake_components: null pointer");
-    if (int s = check_cc("primx_texbake_components", F, U)) return s;
+    PRIMX_TRY(check_cc("primx_texbake_components", F, U));
     *n_comp = 0;
     if (F == 0) return PRIMX_OK;
     PRIMX_REQUIRE(node && ws && comp, "primx_texbake_components: null pointer");
@@ -577,10 +586,7 @@ extern "C" int primx_texbake_components(const int* node, int F, int U, void* ws,
     bool done = false;
     while (!done) {
         PRIMX_REQUIRE(rounds < MAX_ROUNDS, "primx_texbake_components: no convergence after %d rounds", rounds);
-        if (hipMemsetAsync(flags, 0, ROUND_BATCH * sizeof(int), st) != hipSuccess) {
-            primx_set_error("primx_texbake_components: hipMemsetAsync failed");
-            return PRIMX_ELAUNCH;
-        }
+        PRIMX_TRY(zero(flags, ROUND_BATCH * sizeof(int), st, "primx_texbake_components"));
         for (int r = 0; r < ROUND_BATCH; ++r) {
             hipLaunchKernelGGL(tb_cc_hook_kernel, dim3(nblocks(F, THREADS)), dim3(THREADS), 0, st, node, minface, F, U,
                                (const int*)buf[0], buf[y], flags + r);
@@ -592,18 +598,13 @@ extern "C" int primx_texbake_components(const int* node, int F, int U, void* ws,
         }
         rounds += ROUND_BATCH;
         int h[ROUND_BATCH];
-        if (hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            primx_set_error("primx_texbake_components: reading the change flags failed");
-            return PRIMX_ELAUNCH;
-        }
+        PRIMX_TRY(readback(h, flags, sizeof(h), st, "primx_texbake_components"));
         for (int r = 0; r < ROUND_BATCH; ++r) done = done || h[r] == 0;   // a round without change: every later one too
     }
     hipLaunchKernelGGL(tb_cc_count_kernel, dim3(l.nblk), dim3(THREADS), 0, st, (const int*)buf[0], F, bsum);
     PRIMX_CHECK_LAUNCH("primx_texbake_components (count)");
     long long* tot = (long long*)(w + l.tot);
-    hipLaunchKernelGGL(tb_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, bsum, l.nblk, tot);
-    PRIMX_CHECK_LAUNCH("primx_texbake_components (scan)");
+    PRIMX_TRY(scan_blocks(bsum, l.nblk, tot, st, "primx_texbake_components (scan)"));
     int* rank = (int*)(w + l.rank);
     hipLaunchKernelGGL(tb_cc_rank_kernel, dim3(l.nblk), dim3(THREADS), 0, st, (const int*)buf[0], F, (const long long*)bsum,
                        rank);
@@ -612,25 +613,22 @@ extern "C" int primx_texbake_components(const int* node, int F, int U, void* ws,
                        (const int*)rank, F, comp);
     PRIMX_CHECK_LAUNCH("primx_texbake_components (assign)");
     long long ht[2];
-    if (hipMemcpyAsync(ht, tot, sizeof(ht), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        primx_set_error("primx_texbake_components: reading the component count failed");
-        return PRIMX_ELAUNCH;
-    }
+    PRIMX_TRY(readback(ht, tot, sizeof(ht), st, "primx_texbake_components"));
     *n_comp = ht[0];
     return PRIMX_OK;
 }
 
 extern "C" int primx_texbake_raster_workspace(int W, int H, int64_t* bytes) {
     PRIMX_REQUIRE(bytes, "primx_texbake_raster_workspace: null pointer");
-    if (int s = check_atlas("primx_texbake_raster_workspace", W, H)) return s;
+    PRIMX_TRY(check_atlas("primx_texbake_raster_workspace", W, H));
     *bytes = (int64_t)raster_layout(W, H).total;
     return PRIMX_OK;
 }
 
 extern "C" int primx_texbake_raster(const int* uv, const int* ft, int NUV, int F, int W, int H, int* face_id, int* cover,
                                     void* ws, int64_t ws_bytes, int64_t* totals, void* stream) {
-    if (int s = check_atlas("primx_texbake_raster", W, H)) return s;
-    if (int s = check_mesh("primx_texbake_raster", 0, F, NUV)) return s;
+    PRIMX_TRY(check_atlas("primx_texbake_raster", W, H));
+    PRIMX_TRY(check_mesh("primx_texbake_raster", 0, F, NUV));
     PRIMX_REQUIRE(face_id && cover && ws && totals, "primx_texbake_raster: null pointer");
     PRIMX_REQUIRE(F == 0 || (uv && ft), "primx_texbake_raster: null pointer");
     const RasterLayout l = raster_layout(W, H);
@@ -648,16 +646,14 @@ extern "C" int primx_texbake_raster(const int* uv, const int* ft, int NUV, int F
     }
     hipLaunchKernelGGL(tb_cover_count_kernel, dim3(l.nblk), dim3(THREADS), 0, st, face_id, (const int*)cover, HW, bsum);
     PRIMX_CHECK_LAUNCH("primx_texbake_raster (count)");
-    hipLaunchKernelGGL(tb_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, bsum, l.nblk, (long long*)totals);
-    PRIMX_CHECK_LAUNCH("primx_texbake_raster (scan)");
-    return PRIMX_OK;
+    return scan_blocks(bsum, l.nblk, (long long*)totals, st, "primx_texbake_raster (scan)");
 }
 
 extern "C" int primx_texbake_compact(const int* face_id, int W, int H, const void* ws, int64_t ws_bytes, const int* uv,
                                      const int* ft, int NUV, const float* v, const int* f, int V, int F, int64_t n,
                                      int* texel, float* points, void* stream) {
-    if (int s = check_atlas("primx_texbake_compact", W, H)) return s;
-    if (int s = check_mesh("primx_texbake_compact", V, F, NUV)) return s;
+    PRIMX_TRY(check_atlas("primx_texbake_compact", W, H));
+    PRIMX_TRY(check_mesh("primx_texbake_compact", V, F, NUV));
     PRIMX_REQUIRE(n >= 0 && n <= (int64_t)W * H, "primx_texbake_compact: n = %lld is not a count of texels", (long long)n);
     if (n == 0) return PRIMX_OK;
     PRIMX_REQUIRE(face_id && ws && uv && ft && v && f && texel && points, "primx_texbake_compact: null pointer");
@@ -672,28 +668,27 @@ extern "C" int primx_texbake_compact(const int* face_id, int W, int H, const voi
 
 extern "C" int primx_texbake_fill_workspace(int W, int H, int64_t* bytes) {
     PRIMX_REQUIRE(bytes, "primx_texbake_fill_workspace: null pointer");
-    if (int s = check_atlas("primx_texbake_fill_workspace", W, H)) return s;
-    *bytes = (int64_t)(align_up((size_t)W * H * 8) + align_up((size_t)W * H));
+    PRIMX_TRY(check_atlas("primx_texbake_fill_workspace", W, H));
+    *bytes = (int64_t)fill_layout(W, H).total;
     return PRIMX_OK;
 }
 
 extern "C" int primx_texbake_fill(const float* attr, const int* texel, int64_t n, const int* face_id, int W, int H,
                                   int radius, int band, void* ws, int64_t ws_bytes, uint8_t* albedo,
                                   uint8_t* metallic_roughness, void* stream) {
-    if (int s = check_atlas("primx_texbake_fill", W, H)) return s;
+    PRIMX_TRY(check_atlas("primx_texbake_fill", W, H));
     PRIMX_REQUIRE(radius >= 1 && radius <= MAX_RADIUS, "primx_texbake_fill: radius must be in [1, %d] (got %d)", MAX_RADIUS,
                   radius);
     PRIMX_REQUIRE(band >= 1 && band <= MAX_BAND, "primx_texbake_fill: band must be in [1, %d] (got %d)", MAX_BAND, band);
     PRIMX_REQUIRE(n >= 0 && n <= (int64_t)W * H, "primx_texbake_fill: n = %lld is not a count of texels", (long long)n);
     PRIMX_REQUIRE(face_id && ws && albedo && metallic_roughness, "primx_texbake_fill: null pointer");
     PRIMX_REQUIRE(n == 0 || (attr && texel), "primx_texbake_fill: null pointer");
-    const size_t img_bytes = align_up((size_t)W * H * 8);
-    PRIMX_REQUIRE(ws_bytes >= (int64_t)(img_bytes + align_up((size_t)W * H)),
-                  "primx_texbake_fill: workspace of %lld bytes, need %lld", (long long)ws_bytes,
-                  (long long)(img_bytes + align_up((size_t)W * H)));
+    const FillLayout l = fill_layout(W, H);
+    PRIMX_REQUIRE(ws_bytes >= (int64_t)l.total, "primx_texbake_fill: workspace of %lld bytes, need %lld", (long long)ws_bytes,
+                  (long long)l.total);
     hipStream_t st = (hipStream_t)stream;
-    uint8_t* img = (uint8_t*)ws;
-    uint8_t* bandmap = img + img_bytes;
+    uint8_t* img = (uint8_t*)ws + l.img;
+    uint8_t* bandmap = (uint8_t*)ws + l.band;
     const int HW = W * H;
     if (n > 0) {
         hipLaunchKernelGGL(tb_scatter_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, attr, texel, (long long)n, HW,
@@ -710,7 +705,7 @@ extern "C" int primx_texbake_fill(const float* attr, const int* texel, int64_t n
 
 extern "C" int primx_texbake_tangents(const float* nrm, const int* ft, const int* label, int NUV, int F, float* tangent,
                                       void* stream) {
-    if (int s = check_mesh("primx_texbake_tangents", 0, F, NUV)) return s;
+    PRIMX_TRY(check_mesh("primx_texbake_tangents", 0, F, NUV));
     PRIMX_REQUIRE(4 * (int64_t)NUV < I31, "primx_texbake_tangents: 4 * NUV must be < 2^31 (got NUV = %d)", NUV);
     if (F == 0) return PRIMX_OK;
     PRIMX_REQUIRE(nrm && ft && label && tangent, "primx_texbake_tangents: null pointer");
@@ -724,8 +719,8 @@ extern "C" int primx_texbake_tangents(const float* nrm, const int* ft, const int
 extern "C" int primx_texbake_normal_texels(const int* texel, int64_t n, const int* face_id, int W, int H, const int* uv,
                                            const int* ft, int NUV, int F, const float* nrm, const float* tangent,
                                            const float* g, float* nts, float* attr, void* stream) {
-    if (int s = check_atlas("primx_texbake_normal_texels", W, H)) return s;
-    if (int s = check_mesh("primx_texbake_normal_texels", 0, F, NUV)) return s;
+    PRIMX_TRY(check_atlas("primx_texbake_normal_texels", W, H));
+    PRIMX_TRY(check_mesh("primx_texbake_normal_texels", 0, F, NUV));
     PRIMX_REQUIRE(4 * (int64_t)NUV < I31, "primx_texbake_normal_texels: 4 * NUV must be < 2^31 (got NUV = %d)", NUV);
     PRIMX_REQUIRE(n >= 0 && n <= (int64_t)W * H, "primx_texbake_normal_texels: n = %lld is not a count of texels", (long long)n);
     if (n == 0) return PRIMX_OK;

@@ -47,7 +47,7 @@ DEV = "cuda:0"
 pytestmark = pytest.mark.gpu
 KW = dict(v_pct=1, min_f=8, min_d=5)                 # inference.py:126
 KW_CAPPED = dict(v_pct=0.3, min_f=64, min_d=20)      # the existing small-v_pct case: the merge grid is at its cap
-PTS, SCAN_THREADS = 1024, 1024                       # block_scan.h / mcubes.hip: items per block sum, scan threads
+PTS, SCAN_THREADS = 1024, 1024                       # csrc/mesh_common.h: items per block sum, scan threads
 ATTRS = ("v", "f", "normals", "albedo", "roughness", "metallic")
 _CACHE = {}
 
