@@ -19,6 +19,8 @@
 //   compact:    covered texels in raster order (ballot / mbcnt block prefix), each with the 3-D point of its barycentrics.
 //   fill:       scatter of the quantized bytes, band map, then per 16 x 16 tile the nearest band texel inside a
 //               (2R + 1)^2 window held in LDS.
+//   occlusion:  ambient occlusion of the SDF lattice (no counterpart in the reference): one thread per covered texel marches
+//               K directions x J trilinear samples through the lattice, rules A1-A4 of include/primx_hip.h; gather-bound.
 #include <algorithm>
 #include <utility>
 
@@ -378,6 +380,72 @@ __global__ __launch_bounds__(THREADS) void tb_normal_texels_kernel(const int* __
     }
 }
 
+// ------------------------------------------------------------------ ambient occlusion of the lattice
+
+constexpr int MAX_DIRS = 256;
+constexpr int MAX_STEPS = 64;
+constexpr int MAX_LATTICE = 1024;
+
+__device__ __forceinline__ float lerp1(float p, float q, float t) { return p + t * (q - p); }
+
+// rule A1 of include/primx_hip.h; the clamp keeps every index inside [0, R - 1] whatever x holds (fmaxf drops a NaN)
+__device__ __forceinline__ float occ_phi(const float* __restrict__ lat, int R, float rm1, const float* x, float iso) {
+    size_t cell[3];
+    float f[3];
+    for (int a = 0; a < 3; ++a) {
+        const float c = fminf(fmaxf(x[a], -1.f), 1.f);
+        const float u = ((c + 1.f) * 0.5f) * rm1;
+        const int i = max(0, min((int)floorf(u), R - 2));
+        cell[a] = (size_t)i;
+        f[a] = u - (float)i;
+    }
+    const size_t r = (size_t)R;
+    const float* p0 = lat + (cell[0] * r + cell[1]) * r + cell[2];       // x, y
+    const float* p1 = p0 + r;                                            // x, y + 1
+    const float* p2 = p0 + r * r;                                        // x + 1, y
+    const float* p3 = p2 + r;                                            // x + 1, y + 1
+    const float z00 = lerp1(p0[0], p0[1], f[2]), z01 = lerp1(p1[0], p1[1], f[2]);
+    const float z10 = lerp1(p2[0], p2[1], f[2]), z11 = lerp1(p3[0], p3[1], f[2]);
+    return lerp1(lerp1(z00, z01, f[1]), lerp1(z10, z11, f[1]), f[0]) - iso;
+}
+
+// rules A2-A4; one thread per texel (raster order: neighbouring lanes walk neighbouring cells), the directions in LDS (every lane
+// reads the same address: a broadcast)
+__global__ __launch_bounds__(THREADS) void tb_occlusion_kernel(const float* __restrict__ lat, int R, const float* __restrict__ pts,
+                                                               const float* __restrict__ nrm, long long n,
+                                                               const float* __restrict__ dirs, int K, int J, float radius,
+                                                               float bias, float iso, float* __restrict__ occ) {
+    __shared__ float s_dir[3 * MAX_DIRS];
+    for (int q = threadIdx.x; q < 3 * K; q += THREADS) s_dir[q] = dirs[q];
+    __syncthreads();
+    const long long k = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (k >= n) return;
+    const float rm1 = (float)(R - 1);
+    const float h = __fdiv_rn(2.f, rm1), fj = (float)J;
+    const float N[3] = {nrm[3 * k], nrm[3 * k + 1], nrm[3 * k + 2]};
+    float o[3];
+    for (int a = 0; a < 3; ++a) o[a] = pts[3 * k + a] + bias * N[a];
+    const float phi0 = fmaxf(occ_phi(lat, R, rm1, o, iso), 0.5f * h);
+    float num = 0.f, den = 0.f;
+    for (int d = 0; d < K; ++d) {
+        const float* D = s_dir + 3 * d;
+        const float c = fmaxf(0.f, dot3(N, D));
+        if (!(c > 0.f)) continue;
+        float m = 0.f;
+        for (int j = 0; j < J; ++j) {
+            const float t = __fdiv_rn(radius * (float)(j + 1), fj);
+            const float x[3] = {o[0] + t * D[0], o[1] + t * D[1], o[2] + t * D[2]};
+            const float v = occ_phi(lat, R, rm1, x, iso);
+            m = j == 0 ? v : fminf(m, v);
+            if (m <= 0.f) break;                                         // V is 0 from here on
+        }
+        const float V = fminf(fmaxf(__fdiv_rn(m, phi0), 0.f), 1.f);
+        num += c * (1.f - V);
+        den += c;
+    }
+    occ[k] = den > 0.f ? 1.f - __fdiv_rn(num, den) : 1.f;
+}
+
 // ------------------------------------------------------------------ quantize + fill
 
 __device__ __forceinline__ uint8_t quant(float x) {
@@ -728,5 +796,22 @@ extern "C" int primx_texbake_normal_texels(const int* texel, int64_t n, const in
     hipLaunchKernelGGL(tb_normal_texels_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, texel,
                        (long long)n, face_id, W, W * H, uv, ft, NUV, F, nrm, tangent, g, nts, attr);
     PRIMX_CHECK_LAUNCH("primx_texbake_normal_texels");
+    return PRIMX_OK;
+}
+
+extern "C" int primx_texbake_occlusion(const float* lattice, int R, const float* pts, const float* nrm, int64_t n,
+                                       const float* dirs, int K, int steps, float radius, float bias, float isovalue, float* occ,
+                                       void* stream) {
+    PRIMX_REQUIRE(R >= 2 && R <= MAX_LATTICE, "primx_texbake_occlusion: R must be in [2, %d] (got %d)", MAX_LATTICE, R);
+    PRIMX_REQUIRE(K >= 1 && K <= MAX_DIRS, "primx_texbake_occlusion: K must be in [1, %d] (got %d)", MAX_DIRS, K);
+    PRIMX_REQUIRE(steps >= 1 && steps <= MAX_STEPS, "primx_texbake_occlusion: steps must be in [1, %d] (got %d)", MAX_STEPS, steps);
+    PRIMX_REQUIRE(radius > 0.f && bias >= 0.f, "primx_texbake_occlusion: need radius > 0 and bias >= 0 (got %g, %g)", (double)radius,
+                  (double)bias);
+    PRIMX_REQUIRE(n >= 0 && n < I31, "primx_texbake_occlusion: n must be in [0, 2^31) (got %lld)", (long long)n);
+    if (n == 0) return PRIMX_OK;
+    PRIMX_REQUIRE(lattice && pts && nrm && dirs && occ, "primx_texbake_occlusion: null pointer");
+    hipLaunchKernelGGL(tb_occlusion_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, lattice, R, pts, nrm,
+                       (long long)n, dirs, K, steps, radius, bias, isovalue, occ);
+    PRIMX_CHECK_LAUNCH("primx_texbake_occlusion");
     return PRIMX_OK;
 }

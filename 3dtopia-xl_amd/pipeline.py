@@ -230,7 +230,8 @@ def primitives_to_texmesh(recon_param_b: torch.Tensor, resolution: int = 256, te
     through `mesh.extract_texmesh(field, resolution, texture_size, **kw)` - the UV-mapped PBR GLB of inference.py:86-225
     `clean=True` adds the reference's `clean_mesh` step and `decimate=N` its `decimate_mesh` step (`mesh.DECIMATE_TARGET`
     = 100000 in its configuration) before the bake; `normal_map=True` also bakes the field's normals into a tangent-space
-    normal map (TANGENT + normalTexture in the GLB)."""
+    normal map (TANGENT + normalTexture in the GLB); `occlusion=True` bakes ambient occlusion from the SDF lattice into R of
+    the metallic-roughness image (occlusionTexture in the GLB)."""
     from .mesh import extract_texmesh
     from .primsdf import PrimSDF
     if recon_param_b.dim() != 2:

@@ -11,7 +11,7 @@ inference.py:312-352 does it:
 There are no checkpoints offline: every network carries random weights, so the outputs are noise - the point is the
 data flow, the shapes and the per-stage timing.
     python examples/generate.py [--steps 25] [--sampler ddim|dpm] [--res 128] [--lattice 96] [--mesh OUT.glb [--mesh-res 256]]
-                                [--texmesh OUT.glb [--texture-size 1024] [--normal-map]] [--clean] [--decimate N]
+                                [--texmesh OUT.glb [--texture-size 1024] [--normal-map] [--occlusion]] [--clean] [--decimate N]
 """
 import argparse
 import os
@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--texture-size", type=int, default=1024, help="texture edge of --texmesh (the reference's 1024)")
     ap.add_argument("--normal-map", action="store_true", help="also bake the field's normals into a tangent-space normal map "
                     "of --texmesh (TANGENT + normalTexture): the detail --decimate removes from the geometry")
+    ap.add_argument("--occlusion", action="store_true", help="also bake ambient occlusion from the SDF lattice into R of the "
+                    "metallic-roughness image of --texmesh (occlusionTexture); the defaults' look on real assets is unmeasured")
     ap.add_argument("--clean", action="store_true", help="clean the --mesh / --texmesh mesh after marching cubes with "
                     "inference.py:126's clean_mesh arguments (mesh.CLEAN_ARGS)")
     ap.add_argument("--decimate", type=int, default=0, help="then decimate the --mesh / --texmesh mesh to at most N faces "
@@ -130,11 +132,11 @@ def main():
     if a.texmesh:
         tm = timed(f"textured mesh, {a.mesh_res}^3 lattice, {a.texture_size}^2 textures",
                    lambda: pipeline.primitives_to_texmesh(recon[0], a.mesh_res, a.texture_size, clean=a.clean,
-                                                          decimate=a.decimate, stats=dstats, normal_map=a.normal_map))
+                                                          decimate=a.decimate, stats=dstats, normal_map=a.normal_map, occlusion=a.occlusion))
         report_decimation()
         tm.write_glb(a.texmesh)
         print(f"textured mesh: {tm.v.shape[0]} vertices, {tm.f.shape[0]} triangles, "
-              f"{int(tm.covered.sum())} covered texels{', normal map' if tm.normal_map is not None else ''} -> {a.texmesh}")
+              f"{int(tm.covered.sum())} covered texels{', normal map' if tm.normal_map is not None else ''}{', occlusion' if tm.occlusion else ''} -> {a.texmesh}")
 
 
 if __name__ == "__main__":

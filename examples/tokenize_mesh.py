@@ -15,7 +15,7 @@ random weights (the tokens are then noise: the point is the data flow and the pe
 tokenize.py: a script directory is searched for modules first, and that name would replace the standard library's `tokenize`
 for every script in examples/.)
 
-    python examples/tokenize_mesh.py [--mesh IN.ply | IN.glb] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--normal-map] [--vae VAE.pt] [--denoised OUT.pt]
+    python examples/tokenize_mesh.py [--mesh IN.ply | IN.glb] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--normal-map] [--occlusion] [--vae VAE.pt] [--denoised OUT.pt]
 """
 import argparse
 import math
@@ -50,6 +50,8 @@ def main():
                     help="input mesh: a binary PLY as TriMesh.write_ply writes it, or a glTF 2.0 .glb; a torus when absent")
     ap.add_argument("--texture-size", type=int, default=1024, help="texture size of the GLBs written")
     ap.add_argument("--normal-map", action="store_true", help="bake a tangent-space normal map of the field into the GLBs written")
+    ap.add_argument("--occlusion", action="store_true", help="bake ambient occlusion from the SDF lattice into R of the metallic-roughness "
+                    "image of the GLBs written (occlusionTexture)")
     ap.add_argument("--out", default="tokenized.ply", help="the mesh extracted from the fitted primitives")
     ap.add_argument("--denoised", default=None, help="also save the primitives as a denoised.pt")
     ap.add_argument("--prims", type=int, default=2048)
@@ -117,7 +119,7 @@ def main():
         report(field, "refined")
     glb_out = os.path.splitext(a.out)[0] + ".glb"
     if is_glb:
-        tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size, normal_map=a.normal_map))
+        tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size, normal_map=a.normal_map, occlusion=a.occlusion))
         print(f"  V = {tex.v.shape[0]}  F = {tex.f.shape[0]}")
         tex.write_glb(glb_out)
         print("extracted textured mesh ->", glb_out)
@@ -128,7 +130,7 @@ def main():
         print("extracted mesh ->", a.out)
     if a.ply is None:
         # close the loop on this project's own textured GLB: tokens -> GLB -> read_glb -> tokens
-        tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size, normal_map=a.normal_map))
+        tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size, normal_map=a.normal_map, occlusion=a.occlusion))
         tex.write_glb(glb_out)
         back = timed("read_glb (the GLB just written)", lambda: pipeline.read_glb(glb_out, device=dev))
         print(f"  V = {back.v.shape[0]}  F = {back.f.shape[0]}  images " + ", ".join(f"{i.shape[1]}x{i.shape[0]}" for i in back.images))

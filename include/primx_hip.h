@@ -815,6 +815,36 @@ int primx_texbake_normal_texels(const int* texel, int64_t n, const int* face_id,
                                 int NUV, int F, const float* nrm, const float* tangent, const float* g, float* nts,
                                 float* attr, void* stream);
 
+/* Ambient occlusion of the SDF lattice at the covered texels (no counterpart in the reference, whose "NA" channel stays 0; glTF
+ * 2.0 section 3.9.3 "Occlusion texture": R of the metallic-roughness image).  Added to ABI 35 without a new number: no existing
+ * call changes.  The estimator is this project's choice.  fp32 throughout, no FMA contraction, IEEE division, no fast-math
+ * intrinsic; every sum in the order written.
+ *
+ * lattice [R, R, R] fp32 = the field at lattice[ix, iy, iz] <-> (lin[ix], lin[iy], lin[iz]), lin = linspace(-1, 1, R) (element
+ * (ix R + iy) R + iz, indexed in 64 bits); pts [n, 3] fp32; nrm [n, 3] fp32 unit normals (an all-zero row is allowed); dirs
+ * [K, 3] fp32 unit directions over the WHOLE sphere (mesh.occlusion_directions); steps = J; radius, bias, isovalue fp32 ->
+ * occ [n] fp32 in [0, 1], 1 = open.
+ *   A1  phi(x) = trilinear(lattice, clamp(x, -1, 1)) - isovalue.  Per axis c = min(max(x, -1), 1), u = ((c + 1) * 0.5) *
+ *       fp32(R - 1), cell i = min(int(floor(u)), R - 2), f = u - fp32(i).  With the eight corners v_abc (a, b, c = offsets in
+ *       x, y, z) and lerp(p, q, t) = p + t (q - p): along z first, z_ab = lerp(v_ab0, v_ab1, f_z); then y, y_a = lerp(z_a0,
+ *       z_a1, f_y); then x, lerp(y_0, y_1, f_x); then - isovalue.  Clamping the POSITION (edge extension) keeps phi continuous
+ *       everywhere; a surface that touches a face of the cube sees the constant extension as a wall of its own value beyond the
+ *       face and can be darkened slightly by it.
+ *   A2  h = 2 / fp32(R - 1).  o = p + bias n (per component), phi0 = max(phi(o), 0.5 h).
+ *   A3  For every direction k in table order: c_k = max(0, (n_x d_x + n_y d_y) + n_z d_z).  c_k == 0 contributes exactly 0 and is
+ *       skipped.  Otherwise m_k = min over j = 0 .. J - 1, in that order, of phi(o + t_j d_k) (per component o + t_j d), t_j =
+ *       (radius * fp32(j + 1)) / fp32(J); V_k = min(max(m_k / phi0, 0), 1).  (A ray may stop at its first sample with phi <= 0:
+ *       V_k is 0 from there on whatever follows.)  num += c_k * (1 - V_k), den += c_k, both from 0.
+ *   A4  occ = 1 - num / den where den > 0, else 1 (a zero normal).
+ * An unoccluded texel (every m_k >= phi0) is exactly 1.0f.  The fixed world-space direction set with the cosine weight needs no
+ * tangent frame, so the map is continuous in p, n and the lattice; dividing by phi0 makes a flat or convex neighbourhood come out
+ * at 1 whatever the gradient's magnitude (the field is a learned SDF, not an exact one).
+ * One launch, one thread per texel, the direction table in LDS; no atomics, no workspace, no read-back; bitwise deterministic.
+ * Requires 2 <= R <= 1024, 1 <= K <= 256, 1 <= steps <= 64, radius > 0, bias >= 0, 0 <= n < 2^31 and, for n > 0, non-null
+ * pointers; n == 0 launches nothing and returns OK. */
+int primx_texbake_occlusion(const float* lattice, int R, const float* pts, const float* nrm, int64_t n, const float* dirs, int K,
+                            int steps, float radius, float bias, float isovalue, float* occ, void* stream);
+
 /* ----------------------------------------------------------------------------------------------
  * Mesh cleanup (inference.py:126: clean_mesh(v, f, min_f=8, min_d=5, repair=True, remesh=False), the pymeshlab filters
  * of utils/meshutils.py:118-193).  ABI 29.

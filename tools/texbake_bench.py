@@ -5,11 +5,14 @@ texels, the fp32 field query, the quantize + fill, and the PNG / GLB write.  Two
 examples/generate.py poses a random-weight sample (scale 0.05-0.08, centres in [-0.6, 0.6]^3, random payload).  Each
 stage is timed with a device synchronisation around it, median of --reps runs after one warm-up.
 
-    python tools/texbake_bench.py [--reps 5] [--sizes 1024 2048] [--normal-map]
+    python tools/texbake_bench.py [--reps 5] [--sizes 1024 2048] [--normal-map] [--occlusion]
 
 --normal-map adds the rows of the tangent-space normal map (mesh.bake_normal_map, stage by stage): the field's gradient query
 at the texel points, the tangents, the texel normals, the second fill, the GLB write with the third PNG, and the total of
-`bake_textures(normal_map=True)` next to the plain one.
+`bake_textures(normal_map=True)` next to the plain one.  --occlusion adds the rows of the ambient occlusion, each on its own:
+the SDF lattice (`field_lattice`; `extract_texmesh` reuses the one marching cubes read instead), the field normals, the
+occlusion kernel (`texel_occlusion`, default arguments), the extra fill that carries it into R, and the totals of
+`bake_textures(occlusion=True)` with the lattice handed over and computed.
 """
 import argparse
 import os
@@ -35,7 +38,7 @@ def stage(name, fn, times):
     return out
 
 
-def bake_stages(M, field, mesh, size, times, normal_map=False):
+def bake_stages(M, field, mesh, size, times, normal_map=False, occlusion=False, resolution=256):
     """mesh.bake_textures, stage by stage (the same calls)."""
     v, f, n = mesh.v, mesh.f, mesh.normals
     nv, nf = v.shape[0], f.shape[0]
@@ -72,6 +75,16 @@ def bake_stages(M, field, mesh, size, times, normal_map=False):
         with tempfile.TemporaryDirectory() as d:
             stage("normal map: GLB write with 3 PNGs", lambda: tm.write_glb(os.path.join(d, "m.glb")), times)
         stage("bake_textures(normal_map=True) total", lambda: M.bake_textures(field, mesh, size, normal_map=True), times)
+    if occlusion:
+        lattice = stage("occlusion: lattice (reused by extract_texmesh)", lambda: M.field_lattice(field, resolution), times)
+        g = stage("occlusion: field normals", lambda: M.field_normals(field, pts), times)
+        dirs = M.occlusion_directions().to(v.device)
+        ao = stage("occlusion: kernel", lambda: M.texel_occlusion(lattice, pts, g, dirs), times)
+        stage("occlusion: quantize + fill with the extra fill", lambda: M.fill_textures(attr, texel, atlas.face_id, occlusion=ao), times)
+        stage("bake_textures(occlusion=True, lattice=) total", lambda: M.bake_textures(field, mesh, size, occlusion=True, lattice=lattice),
+              times)
+        stage("bake_textures(occlusion=True) total, own lattice",
+              lambda: M.bake_textures(field, mesh, size, occlusion=True, occlusion_resolution=resolution), times)
     return atlas, nc
 
 
@@ -81,6 +94,7 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[1024, 2048])
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--normal-map", action="store_true", help="also time the stages of the tangent-space normal map")
+    ap.add_argument("--occlusion", action="store_true", help="also time the stages of the ambient occlusion bake")
     a = ap.parse_args()
     __graft_entry__.build()
     from topia_xl_amd import mesh as M
@@ -100,7 +114,7 @@ def main():
                 continue
             for rep in range(a.reps + 1):
                 t = {}
-                atlas, nc = bake_stages(M, field, mesh, size, t, a.normal_map)
+                atlas, nc = bake_stages(M, field, mesh, size, t, a.normal_map, a.occlusion, a.resolution)
                 if rep:
                     for k, x in t.items():
                         times.setdefault(k, []).extend(x)
@@ -112,8 +126,8 @@ def main():
                   f"split rounds {atlas.split_rounds}, covered texels {atlas.n_covered} ({atlas.coverage:.3f}), "
                   f"scale {atlas.scale:.1f} texels / unit", flush=True)
             for k, x in med.items():
-                print(f"    {k:40s} {x:9.2f} ms", flush=True)
-            print(f"    {'host packing + atlas arrays (derived)':40s} {pack:9.2f} ms", flush=True)
+                print(f"    {k:48s} {x:9.2f} ms", flush=True)
+            print(f"    {'host packing + atlas arrays (derived)':48s} {pack:9.2f} ms", flush=True)
 
 
 if __name__ == "__main__":
