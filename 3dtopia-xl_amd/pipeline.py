@@ -225,6 +225,14 @@ def primitives_to_mesh(recon_param_b: torch.Tensor, resolution: int = 256, **kw)
     return extract_mesh(m.eval(), resolution, **kw)
 
 
+def primitives_vs_mesh(recon_param_b: torch.Tensor, mesh, resolution: int = 256, **kw) -> dict:
+    """recon_param[b] [N, 4 + 6 S^3] and a mesh in the primitives' coordinates (`info['v']`, `info['f']` of `mesh_to_primitives`)
+    -> `metrics.compare_meshes(mesh, primitives_to_mesh(recon_param_b, resolution), **kw)`: Chamfer distance, F-score, Hausdorff
+    distance and normal consistency of the round trip mesh -> primitives -> mesh (metrics.py states the definitions)."""
+    from .metrics import compare_meshes
+    return compare_meshes(mesh, primitives_to_mesh(recon_param_b, resolution), **kw)
+
+
 def primitives_to_texmesh(recon_param_b: torch.Tensor, resolution: int = 256, texture_size: int = 1024, **kw):
     """recon_param[b] [N, 4 + 6 S^3] -> `mesh.TexturedMesh`: the sample's primitives (as `primitives_to_mesh` builds them)
     through `mesh.extract_texmesh(field, resolution, texture_size, **kw)` - the UV-mapped PBR GLB of inference.py:86-225

@@ -10,12 +10,14 @@ voxel) and comes back as a textured GLB: `extract_texmesh` -> `TexturedMesh.writ
 written first and read back, so the run is end to end on a written PLY, and the loop is then closed on a GLB as well: the fitted
 torus is extracted as a textured GLB, that file is read back with `read_glb` and fitted again.  The fit is the
 initialisation the 3DTopia-XL paper describes; --refine N follows it with N steps of gradient refinement against the mesh's own
-field and reports the field error at the surface candidates before and after.  Without --vae the encoder carries
+field and reports the field error at the surface candidates before and after; --metrics prints the round trip's Chamfer distance, F-score, Hausdorff
+distance and normal consistency (`metrics.compare_to_field`: the mesh extracted from the fitted field against the input's exact
+surface).  Without --vae the encoder carries
 random weights (the tokens are then noise: the point is the data flow and the per-stage timing).  (The file is not called
 tokenize.py: a script directory is searched for modules first, and that name would replace the standard library's `tokenize`
 for every script in examples/.)
 
-    python examples/tokenize_mesh.py [--mesh IN.ply | IN.glb] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--normal-map] [--occlusion] [--vae VAE.pt] [--denoised OUT.pt]
+    python examples/tokenize_mesh.py [--mesh IN.ply | IN.glb] [--out OUT.ply] [--prims 2048] [--refine N] [--resolution 256] [--normal-map] [--occlusion] [--metrics] [--vae VAE.pt] [--denoised OUT.pt]
 """
 import argparse
 import math
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--normal-map", action="store_true", help="bake a tangent-space normal map of the field into the GLBs written")
     ap.add_argument("--occlusion", action="store_true", help="bake ambient occlusion from the SDF lattice into R of the metallic-roughness "
                     "image of the GLBs written (occlusionTexture)")
+    ap.add_argument("--metrics", action="store_true", help="print the round trip's quality metrics (metrics.compare_to_field, surface=True)")
     ap.add_argument("--out", default="tokenized.ply", help="the mesh extracted from the fitted primitives")
     ap.add_argument("--denoised", default=None, help="also save the primitives as a denoised.pt")
     ap.add_argument("--prims", type=int, default=2048)
@@ -128,6 +131,10 @@ def main():
         print(f"  V = {out.v.shape[0]}  F = {out.f.shape[0]}")
         out.write_ply(a.out)
         print("extracted mesh ->", a.out)
+    if a.metrics:
+        from topia_xl_amd import metrics
+        rt = timed(f"compare_to_field {a.resolution}^3, surface=True", lambda: metrics.compare_to_field((info["v"], info["f"]), field, a.resolution, surface=True))
+        print("  round trip:", rt)
     if a.ply is None:
         # close the loop on this project's own textured GLB: tokens -> GLB -> read_glb -> tokens
         tex = timed(f"extract_texmesh {a.resolution}^3, {a.texture_size}^2", lambda: M.extract_texmesh(field, a.resolution, a.texture_size, normal_map=a.normal_map, occlusion=a.occlusion))

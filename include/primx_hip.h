@@ -1158,6 +1158,42 @@ int primx_material_sample(const float* uv, const float* vattr, const int* face, 
                           const float* mat_factor, const int* mat_tex, int M, const int64_t* tex_desc, int T,
                           const uint8_t* texels, int64_t n_texels, int* status, float* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Quality metrics (csrc/metrics.hip; added to ABI 35 without a new number: both calls are purely additive).  How far one surface
+ * is from another, in the form in which Chamfer distance, F-score, Hausdorff distance and normal consistency are defined and
+ * published: nearest neighbours between two point sets, then sums, a maximum and threshold counts of the per-point distances.
+ * The reference has no evaluation code; tests/metrics_numpy.py restates the rules below in float32 / float64.  Every expression is
+ * evaluated as written, uncontracted.  Neither call synchronises the stream, reads anything back or uses an atomic: two runs
+ * give the same bits.
+ * -------------------------------------------------------------------------------------------- */
+
+/* The nearest point of b [m, 3] for every point of a [n, 3] (fp32) -> dist [n] fp32, idx [n] int32.
+ *   N1  d2(i, j) = (dx dx + dy dy) + dz dz with dx = a[i].x - b[j].x, dy and dz likewise, in fp32 (primx_fps's expression).
+ *   N2  best = +inf, idx = 0; for j = 0 .. m - 1 in that order: if d2(i, j) < best (strictly) then best = d2(i, j), idx = j.  The
+ *       lowest index wins among equals; a pair whose d2 is NaN or +inf never wins, so a point without a finite pair keeps
+ *       (+inf, 0).
+ *   N3  dist[i] = sqrtf(best).
+ * Brute force by design (n m pairs), b streamed through LDS in chunks of 1024 points; no workspace.  The point index i is 64
+ * bits wide; m >= 1 and 3 m stays below 2^31.  n == 0 launches nothing and returns OK. */
+int primx_nearest_points(const float* a, int64_t n, const float* b, int m, float* dist, int* idx, void* stream);
+
+/* The reduction of per-point results: dist [n] fp32 and idx [n] int32 as primx_nearest_points wrote them (or the dist and face of
+ * primx_mesh_field_query), na [n, 3] and nb [*, 3] fp32 normals of the points and of what idx points into (idx[i] must be a row
+ * of nb: not checked), tau = T thresholds, 0 <= T <= 8, in HOST memory, read before the call returns -> out [4 + T] float64 in
+ * device memory:
+ *   S1  out[0] = sum of (double)dist[i].
+ *   S2  out[1] = sum of (double)dist[i] * (double)dist[i].
+ *   S3  out[2] = max(0, max of dist[i]) (a NaN is passed over); 0 for n == 0.
+ *   S4  out[3] = sum of (double)|(na[i].x nb[k].x + na[i].y nb[k].y) + na[i].z nb[k].z|, k = idx[i], the dot product and the absolute
+ *       value in fp32.  0 when na or nb is NULL; idx may then be NULL as well.
+ *   S5  out[4 + t] = the number of i with dist[i] <= tau[t] (an fp32 compare), stored as a double.
+ * Two launches: at most 256 blocks each reduce one contiguous slice (of max(1024, ceil(n / 256)) elements) in float64 in a fixed
+ * order and write their partials to ws; one block then adds the partials in block order.  The order of the sums is fixed but not
+ * sequential: a sum equals the exact one to within (n - 1) 2^-53 sum|x|; counts and the maximum are exact.
+ * ws: 24576 bytes (256 rows of 12 doubles), 8-byte aligned, any contents.  n == 0 writes the empty set's values (all 0). */
+int primx_distance_stats(const float* dist, const int* idx, const float* na, const float* nb, int64_t n, const float* tau, int T,
+                         void* ws, int64_t ws_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
