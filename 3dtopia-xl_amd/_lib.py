@@ -152,6 +152,9 @@ SIGNATURES = {
     "primx_texbake_occlusion": [_p, _i, _p, _p, _l, _p, _i, _i, _f, _f, _f, _p, _p],
     "primx_nearest_points": [_p, _l, _p, _i, _p, _p, _p],
     "primx_distance_stats": [_p, _p, _p, _p, _l, C.POINTER(_f), _i, _p, _l, _p, _p],     # tau: T floats in host memory
+    "primx_mesh_bvh_workspace": [_i, C.POINTER(_l)],
+    "primx_mesh_bvh_build": [_p, _p, _i, _i, _p, _p, _p, _l, _p],
+    "primx_mesh_bvh_query": [_p, _l, _p, _i, _p, _i, _p, _l, _f, _p, _p, _p, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # An alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI.  Version 21 changed the argument
@@ -162,7 +165,7 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # symbol, which `load` finds out with hasattr.  A version-24 build ignores the kv_* tail of PrimxDitForwardFold that came with
 # primx_linear_heads_fold_pair (the host then projects K / V itself).  The normal map's three entry points joined version 35 the same
 # way but are listed with the number 35: under PRIMX_LIB an absent entry point of 35 is skipped like a probed one.  So did the ambient
-# occlusion's primx_texbake_occlusion, and the two entry points of the quality metrics (metrics.py).
+# occlusion's primx_texbake_occlusion, the two entry points of the quality metrics (metrics.py) and the three of the mesh BVH (fit.MeshBVH).
 _PROBE = 0
 _SINCE: dict = {
     **dict.fromkeys(("primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
@@ -187,6 +190,7 @@ _SINCE: dict = {
     **dict.fromkeys(("primx_primsdf_query_grad", "primx_texbake_tangents", "primx_texbake_normal_texels"), 35),   # the normal map
     "primx_texbake_occlusion": 35,                                                               # ambient occlusion, the same way
     **dict.fromkeys(("primx_nearest_points", "primx_distance_stats"), 35),                       # metrics.py, the same way
+    **dict.fromkeys(("primx_mesh_bvh_workspace", "primx_mesh_bvh_build", "primx_mesh_bvh_query"), 35),   # fit.MeshBVH, the same way
     **dict.fromkeys(("primx_material_sample",                                                    # a MeshField with a material
                      "primx_attention_ksplit_mode", "primx_attention_ksplit",                    # without them: attention never splits its keys
                      "primx_gemm_toq64_mode",                                                    # without it: to_q under the null skip on the 128-row tile

@@ -11,7 +11,9 @@ the reference tree: the defaults below are this project's choice, measured on th
 
 Kernels (csrc/meshfield.hip, rules in include/primx_hip.h "Primitive fitting"): `primx_mesh_field_query` (brute force over
 the faces: exact point-triangle distance, generalized winding number, attributes at the closest point),
-`primx_mesh_face_areas`, `primx_mesh_surface_points`, `primx_fps`; csrc/material.hip ("Textured meshes"): `primx_material_sample`
+`primx_mesh_face_areas`, `primx_mesh_surface_points`, `primx_fps`; csrc/meshbvh.hip ("Mesh BVH"): `MeshBVH`, the same query
+through a bounding volume hierarchy (`accel="bvh"`: the same dist, face and attributes bit for bit, the winding number by a
+far-field expansion; `accel=None`, the default, is the brute-force call); csrc/material.hip ("Textured meshes"): `primx_material_sample`
 (the glTF material of a `mesh.MaterialMesh` at the closest point).  Torch does the plumbing: the float64 inclusive sum of the
 areas (on the host, where it is sequential and therefore reproducible to the bit), the seeded uniforms (a CPU generator, as the
 sampler draws its noise), the normalisation and the assembly of `recon_param`.
@@ -27,6 +29,13 @@ from . import _lib, ops
 QUERY_CHUNK = 256          # triangle records per LDS chunk of primx_mesh_field_query (MF_CHUNK of csrc/meshfield.hip)
 RECORD_BYTES = 64
 N_ATTR = 5                 # r, g, b, roughness, metallic
+BVH_LEAF = 8               # faces per leaf of a MeshBVH (LEAF of csrc/meshbvh.hip)
+BVH_NODE_BYTES = 96        # six float4 per node
+BVH_MOMENT_BYTES = 128     # 16 float64 of build scratch per node
+BVH_HEAD_BYTES = 256       # the index-check flag at 0; the vertices' box, the largest |coordinate| and delta (8 fp32) at 64
+BVH_DELTA_SCALE = 2.0 ** -17   # the boxes are inflated by this times the largest |coordinate| (DESIGN.md "Mesh BVH")
+BVH_BETA = 2.0             # a node farther than beta * its radius adds its far-field expansion to the winding number
+ACCELS = (None, "bvh")
 
 
 def _need_cuda(name, *tensors):
@@ -44,11 +53,122 @@ def _mesh_args(v, f):
     return v, f
 
 
+def bvh_layout(F: int) -> dict:
+    """Where a MeshBVH of F faces keeps what, in bytes from the start of its workspace (`layout` of csrc/meshbvh.hip; 'total' is
+    what primx_mesh_bvh_workspace returns): 'recs' [F] 64-byte face records in sorted order, 'orig' [F] int32 (the face each one
+    is), 'nodes' [2 L] of BVH_NODE_BYTES (node 0 unused, 1 the root, L + l leaf l), 'mom' [2 L] of 16 float64, 'part'."""
+    up = lambda x: (x + 15) & ~15   # noqa: E731
+    nleaf = (F + BVH_LEAF - 1) // BVH_LEAF
+    L = 1
+    while L < nleaf:
+        L *= 2
+    recs = BVH_HEAD_BYTES
+    orig = recs + 64 * F
+    nodes = orig + up(4 * F)
+    mom = nodes + BVH_NODE_BYTES * 2 * L
+    part = mom + BVH_MOMENT_BYTES * 2 * L
+    return {"nleaf": nleaf, "L": L, "recs": recs, "orig": orig, "nodes": nodes, "mom": mom, "part": part, "total": part + 8192}
+
+
+def morton_order(x: torch.Tensor) -> torch.Tensor:
+    """The permutation that puts the points x [n, 3] in the order of their 30-bit Morton codes (1024 steps of the longest side of
+    their bounding box): torch plumbing for `sort_points`, no host synchronisation."""
+    lo = x.min(0).values
+    ext = (x.max(0).values - lo).max()
+    s = torch.where(ext > 0, 1024.0 / ext, torch.zeros_like(ext))
+    q = ((x - lo) * s).clamp(0, 1023).nan_to_num(0.0).long()
+    code = torch.zeros(x.shape[0], dtype=torch.int64, device=x.device)
+    for b in range(10):
+        bit = (q >> b) & 1
+        code |= (bit[:, 0] << (3 * b + 2)) | (bit[:, 1] << (3 * b + 1)) | (bit[:, 2] << (3 * b))
+    return torch.sort(code, stable=True).indices
+
+
+class MeshBVH:
+    """The bounding volume hierarchy of a triangle mesh (include/primx_hip.h "Mesh BVH"): built once, here, and reusable for any
+    number of `query` calls.  v [V, 3] float32, f [F, 3] int32 on a HIP device; face indices outside [0, V) raise (the one
+    read-back of the tree: `query` has none and does not make the host wait).  The sort of the faces' Morton keys is torch's.
+    `ws`: the `.ws` of a tree built earlier from the same v and f (a cached one): nothing is built or checked then."""
+
+    def __init__(self, v: torch.Tensor, f: torch.Tensor, ws: Optional[torch.Tensor] = None):
+        _need_cuda("MeshBVH", v, f, ws)
+        self.v, self.f = _mesh_args(v, f)
+        V, F, dev = self.v.shape[0], self.f.shape[0], self.v.device
+        self.layout = bvh_layout(F)
+        if ws is not None:
+            if ws.dtype != torch.uint8 or ws.dim() != 1 or ws.numel() < self.layout["total"] or not ws.is_contiguous():
+                raise ValueError(f"ws must be the {self.layout['total']} bytes of a MeshBVH of {F} faces")
+            self.ws, self.order = ws, None
+            return
+        with torch.cuda.device(dev):
+            lib = _lib.load()
+            nbytes = _lib.C.c_int64(0)
+            _lib.check(lib.primx_mesh_bvh_workspace(F, _lib.C.byref(nbytes)), "primx_mesh_bvh_workspace")
+            assert nbytes.value == self.layout["total"], (nbytes.value, self.layout)
+            self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            keys = torch.empty(F, dtype=torch.int64, device=dev)
+            vp, fp = ops._dev(self.v, "v", torch.float32), ops._dev(self.f, "f", torch.int32)
+            _lib.check(lib.primx_mesh_bvh_build(vp, fp, V, F, None, keys.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                                ops._stream()), "primx_mesh_bvh_build")
+            self.order = torch.sort(keys, stable=True).indices.int().contiguous()
+            _lib.check(lib.primx_mesh_bvh_build(vp, fp, V, F, self.order.data_ptr(), None, self.ws.data_ptr(), self.ws.numel(),
+                                                ops._stream()), "primx_mesh_bvh_build")
+
+    def matches(self, v: torch.Tensor, f: torch.Tensor) -> bool:
+        """Whether this tree was built for a mesh of these shapes on this device (the contents are the caller's business)."""
+        return v.shape[0] == self.v.shape[0] and f.shape[0] == self.f.shape[0] and v.device == self.v.device
+
+    def query(self, x: torch.Tensor, attr: Optional[torch.Tensor] = None, beta: float = BVH_BETA, sort_points: bool = False):
+        """x [n, 3], attr [V, C] or None -> (dist [n], face [n] int32, wn [n], out_attr [n, C] or None): primx_mesh_bvh_query.
+        `sort_points` runs the points in Morton order and scatters the results back (for incoherent point sets; every point's
+        result is the same either way)."""
+        _need_cuda("MeshBVH.query", x, attr)
+        x = x.float().contiguous()
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError(f"x must be [n, 3], got {tuple(x.shape)}")
+        if not float(beta) >= 0:
+            raise ValueError(f"beta must be at least 0, got {beta}")
+        n, F, dev = x.shape[0], self.f.shape[0], self.v.device
+        C = 0 if attr is None else attr.shape[1]
+        if attr is not None:
+            attr = attr.float().contiguous()
+            if attr.shape[0] != self.v.shape[0]:
+                raise ValueError("attr must have one row per vertex")
+        with torch.cuda.device(dev):
+            perm = morton_order(x) if sort_points and n > 1 else None
+            xs = x if perm is None else x[perm].contiguous()
+            dist = torch.empty(n, dtype=torch.float32, device=dev)
+            face = torch.empty(n, dtype=torch.int32, device=dev)
+            wn = torch.empty(n, dtype=torch.float32, device=dev)
+            out = torch.empty(n, C, dtype=torch.float32, device=dev) if C else None
+            _lib.check(_lib.load().primx_mesh_bvh_query(
+                ops._dev(xs, "x", torch.float32), n, ops._dev(self.f, "f", torch.int32), F,
+                ops._dev(attr, "attr", torch.float32) if C else None, C, self.ws.data_ptr(), self.ws.numel(), float(beta),
+                dist.data_ptr(), face.data_ptr(), wn.data_ptr(), out.data_ptr() if C else None, ops._stream()),
+                "primx_mesh_bvh_query")
+            if perm is not None:
+                back = lambda t: torch.empty_like(t).index_copy_(0, perm, t)   # noqa: E731
+                dist, face, wn, out = back(dist), back(face), back(wn), None if out is None else back(out)
+        return dist, face, wn, out
+
+
+def _check_accel(accel):
+    if accel not in ACCELS:
+        raise ValueError(f"accel must be one of {ACCELS}, got {accel!r}")
+    return accel
+
+
 @ops.on_input_device
-def mesh_field_query(x: torch.Tensor, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None):
+def mesh_field_query(x: torch.Tensor, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None,
+                     bvh: Optional[MeshBVH] = None, beta: float = BVH_BETA, sort_points: bool = False):
     """x [n, 3], v [V, 3] float32, f [F, 3] int32, attr [V, C] or None -> (dist [n], face [n] int32, wn [n], out_attr [n, C]
-    or None): primx_mesh_field_query.  Face indices outside [0, V) raise."""
+    or None): primx_mesh_field_query.  Face indices outside [0, V) raise.  With `bvh` (a `MeshBVH` of the same v and f) the
+    tree answers instead (`MeshBVH.query`: the same dist, face and out_attr, wn approximated under `beta`)."""
     _need_cuda("mesh_field_query", x, v, f, attr)
+    if bvh is not None:
+        if not isinstance(bvh, MeshBVH) or not bvh.matches(v, f):
+            raise ValueError("bvh must be a MeshBVH built from the same v and f")
+        return bvh.query(x, attr, beta, sort_points)
     v, f = _mesh_args(v, f)
     x = x.float().contiguous()
     n, F, dev = x.shape[0], f.shape[0], x.device
@@ -109,11 +229,17 @@ class MeshField:
 
     With `material` (a `mesh.MaterialMesh`; its v and f are not used, `v` and `f` are) tex / mat are the mesh's glTF material at
     the closest point instead: the field query interpolates [vt | color | rm] (C = 8) and `primx_material_sample` evaluates
-    factors and textures there.  The tables and the texel blob are uploaded once, here."""
+    factors and textures there.  The tables and the texel blob are uploaded once, here.
 
-    def __init__(self, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None):
+    `accel="bvh"` builds a `MeshBVH` here and answers every query through it: sdf magnitude, face, tex and mat as without it, bit
+    for bit; the sign from the winding number approximated under `beta`.  `accel=None` is the brute-force query."""
+
+    def __init__(self, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None, accel=None,
+                 beta: float = BVH_BETA, sort_points: bool = False):
         _need_cuda("mesh_field", v, f, attr)
         self.v, self.f = _mesh_args(v, f)
+        self.accel, self.beta, self.sort_points = _check_accel(accel), float(beta), bool(sort_points)
+        self.bvh = MeshBVH(self.v, self.f) if accel == "bvh" else None      # built once, for every chunk and refinement step
         self.material = None
         if material is not None:
             if attr is not None:
@@ -132,7 +258,10 @@ class MeshField:
         self.attr = None if attr is None else attr.float().contiguous()
 
     def query(self, x: torch.Tensor) -> dict:
-        dist, face, wn, a = mesh_field_query(x, self.v, self.f, self.attr)
+        if self.bvh is None:
+            dist, face, wn, a = mesh_field_query(x, self.v, self.f, self.attr)
+        else:
+            dist, face, wn, a = self.bvh.query(x, self.attr, self.beta, self.sort_points)
         sdf = torch.where(wn.abs() >= 0.5, -dist, dist)[:, None]
         if self.material is not None:
             a = material_sample(a[:, 0:2], a[:, 2:8], face, *self.material)
@@ -144,8 +273,9 @@ class MeshField:
     __call__ = query
 
 
-def mesh_field(v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None) -> MeshField:
-    return MeshField(v, f, attr, material)
+def mesh_field(v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None, accel=None,
+               beta: float = BVH_BETA) -> MeshField:
+    return MeshField(v, f, attr, material, accel=accel, beta=beta)
 
 
 @ops.on_input_device
@@ -254,7 +384,8 @@ def refine_points(srt: torch.Tensor, samples_per_prim: int, seed: int = 0) -> to
 
 
 def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, samples_per_prim: int = 256, seed: int = 0,
-                      refine_srt: bool = False, weights=(1.0, 1.0, 1.0), lr_srt: Optional[float] = None, chunk: int = 1 << 20):
+                      refine_srt: bool = False, weights=(1.0, 1.0, 1.0), lr_srt: Optional[float] = None, chunk: int = 1 << 20,
+                      accel=None, beta: float = BVH_BETA):
     """`steps` full-batch Adam steps on recon [P, 4 + 6 S^3] (fp32, HIP device) against `field.query` (a `MeshField`, or anything
     returning {'sdf' [n, 1], 'tex' [n, 3], 'mat' [n, 2]}) -> (recon', info).  `recon` itself is not modified.
 
@@ -266,9 +397,16 @@ def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, 
     (default lr / 100: an Adam step moves every element by about its rate, and a centre that drifts by a fraction of a voxel
     without need costs more than the payload gains), after which the scale is clamped to
     REFINE_SCALE_FLOOR.  `info`: 'loss' (the per-step losses BEFORE each step, read back once at the end), 'points',
-    'target'.  The gradient sums are atomic: the last bits differ from run to run."""
+    'target'.  The gradient sums are atomic: the last bits differ from run to run.
+
+    `field` may also be a mesh (anything `mesh_to_primitives` takes, already in the primitives' frame): the field is then built
+    here, with `accel` and `beta` as `MeshField` takes them.  A field that is given keeps its own."""
     from . import primsdf
     _need_cuda("refine_primitives", recon)
+    _check_accel(accel)
+    if not hasattr(field, "query"):
+        v, f, attr, material = _mesh_parts(field, recon.device)
+        field = MeshField(v, f, attr, material, accel=accel, beta=beta)
     if recon.dim() != 2 or recon.dtype != torch.float32:
         raise ValueError("recon must be fp32 [P, 4 + 6 S^3]")
     P = recon.shape[0]
@@ -308,7 +446,7 @@ def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, 
 
 def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candidates: Optional[int] = None, seed: int = 0,
                        normalize: bool = True, extent: float = 0.9, device=None, chunk: int = 1 << 20, refine: int = 0,
-                       refine_kw: Optional[dict] = None):
+                       refine_kw: Optional[dict] = None, accel=None, beta: float = BVH_BETA):
     """mesh: a `mesh.TriMesh`, (v, f, albedo [V, 3], roughness [V], metallic [V]) or a `mesh.MaterialMesh` (e.g. from
     `mesh.read_glb`: colour and material come from its textures and factors) -> (recon_param [P, 4 + 6 S^3], info).
 
@@ -318,7 +456,9 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
     (`primitives_to_latents` applies the x5).  `normalize`: see `normalize_vertices`.  `info` has the normalisation
     (`center`, `scale`: v' = (v - center) * scale), the candidates (`candidates`, `candidate_face`) and the chosen ones (`idx`).
     `refine=N` > 0 follows the initialisation with N steps of `refine_primitives(recon, field, N, **refine_kw)` against the
-    normalised mesh's field (`info['refine']` is its info); 0 is the initialisation alone."""
+    normalised mesh's field (`info['refine']` is its info); 0 is the initialisation alone.  `accel="bvh"` answers the payload's
+    and the refinement's field queries through one `MeshBVH` of the normalised mesh (`MeshField(accel=, beta=)`)."""
+    _check_accel(accel)
     if device is None:
         v0 = mesh[0] if isinstance(mesh, (tuple, list)) else mesh.v
         device = v0.device if isinstance(v0, torch.Tensor) and v0.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -338,7 +478,7 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
         idx, nn = fps(cand, P, 0)
         pos = cand[idx.long()]
         x = (pos[:, None, :] + nn[:, None, None] * _local_grid(S, dev)[None]).reshape(-1, 3)
-        field = MeshField(v, f, attr, material)
+        field = MeshField(v, f, attr, material, accel=accel, beta=beta)
         parts = [field.query(x[lo:lo + chunk]) for lo in range(0, x.shape[0], chunk)]
         sdf = torch.cat([q["sdf"] for q in parts]).reshape(P, S ** 3)
         a = torch.cat([torch.cat([q["tex"], q["mat"]], 1) for q in parts]).reshape(P, S ** 3, N_ATTR)

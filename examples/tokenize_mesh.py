@@ -59,6 +59,8 @@ def main():
     ap.add_argument("--denoised", default=None, help="also save the primitives as a denoised.pt")
     ap.add_argument("--prims", type=int, default=2048)
     ap.add_argument("--refine", type=int, default=0, help="refinement steps after the initialisation (fit.refine_primitives)")
+    ap.add_argument("--accel", choices=["bvh"], default=None,
+                    help="answer the mesh's field queries through a BVH (fit.MeshBVH) instead of brute force over the faces")
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--vae", default=None, help="VAE checkpoint (.pt with 'model_state_dict'); random weights when absent")
@@ -93,8 +95,9 @@ def main():
     else:
         mesh = timed("read_ply", lambda: pipeline.read_ply(path, device=dev))
     print(f"  V = {mesh.v.shape[0]}  F = {mesh.f.shape[0]}")
-    timed("mesh_to_primitives (first call)", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed))
-    recon, info = timed("mesh_to_primitives", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed))
+    timed("mesh_to_primitives (first call)", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed, accel=a.accel))
+    recon, info = timed("mesh_to_primitives" + (f" (accel={a.accel})" if a.accel else ""),
+                        lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed, accel=a.accel))
     print(f"  recon_param {tuple(recon.shape)}  scale {float(recon[:, 0].min()):.4f} .. {float(recon[:, 0].max()):.4f}  "
           f"normalised by x{float(info['scale']):.4f}")
 
@@ -114,7 +117,8 @@ def main():
     report(field, "fitted")
     if a.refine > 0:
         from topia_xl_amd import fit
-        target = fit.MeshField(info["v"], info["f"], material=mesh) if is_glb else fit.MeshField(info["v"], info["f"], info["attr"])
+        target = fit.MeshField(info["v"], info["f"], material=mesh, accel=a.accel) if is_glb else \
+            fit.MeshField(info["v"], info["f"], info["attr"], accel=a.accel)
         fit.refine_primitives(recon, target, 1)                                       # (first call: loads the kernels)
         recon, rinfo = timed(f"refine_primitives, {a.refine} steps", lambda: fit.refine_primitives(recon, target, a.refine))
         print(f"  loss {rinfo['loss'][0]:.3e} -> {rinfo['loss'][-1]:.3e}")

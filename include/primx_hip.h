@@ -1194,6 +1194,60 @@ int primx_nearest_points(const float* a, int64_t n, const float* b, int m, float
 int primx_distance_stats(const float* dist, const int* idx, const float* na, const float* nb, int64_t n, const float* tau, int T,
                          void* ws, int64_t ws_bytes, double* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Mesh BVH (csrc/meshbvh.hip; added to ABI 35 without a new number: the three calls are purely additive).  The field query of
+ * "Primitive fitting" through a bounding volume hierarchy: dist, face and out_attr are primx_mesh_field_query's bit for bit
+ * (the per-pair arithmetic is the same code, csrc/meshfield_pair.h), wn is the far-field approximation of Barill et al. 2018
+ * ("Fast winding numbers for soups and clouds").  tests/meshbvh_numpy.py restates the tree and both walks in float32 and
+ * float64.  Every expression is evaluated as written, uncontracted; dot(a, b) = (ax bx + ay by) + az bz.  The tree is
+ * deterministic: no atomic touches it and every float64 sum has a fixed order.
+ *
+ * Tree.  B1  lo, hi = the bounding box of ALL V vertices, m = the largest |coordinate| of any vertex, delta = m * 2^-17.
+ *   B2  key(t) = code(t) * 2^32 + t; code = the 30-bit Morton code (x in bits 29, 26, ..; y in 28, 25, ..; z in 27, 24, ..) of
+ *       q_k = (int)min(max((c_k - lo_k) * s, 0), 1023), c_k = ((a_k + b_k) + c_k) / 3 in fp32, s = 1024 / ext with ext = the
+ *       longest side max(max(hi_x - lo_x, hi_y - lo_y), hi_z - lo_z), s = 0 when ext is 0 (every code is then 0).
+ *   B3  order = the faces sorted by key, ascending (the keys are distinct).  The caller sorts.  Leaf l holds the faces
+ *       order[8 l .. 8 l + 7] (the last leaf those below F); L = the number of leaves rounded up to a power of two; node 1 is
+ *       the root, 2 i and 2 i + 1 the children of i, L + l leaf l.  A node without faces below it is flagged empty and never
+ *       visited.
+ *   B4  box of a leaf = the fp32 min / max of its faces' vertices, then lo - delta and hi + delta; of an inner node the union of
+ *       its children's boxes.
+ *   B5  moments, in float64 from the fp32 vertices: per face of kind 0 (a zero-area face, as the field query decides it, is in
+ *       the box and adds nothing here) A = 0.5 (b - a) x (c - a), area = sqrt((Ax Ax + Ay Ay) + Az Az), cen = ((a + b) + c) / 3;
+ *       a leaf adds N += A, S += area, T += area cen, M_ij += cen_i A_j over its faces in sorted order from 0; an inner node is
+ *       left + right.  Then p = T / S (the box's centre 0.5 (lo + hi) where S is 0), C_ij = M_ij - p_i N_j (= sum (cen - p) (x) A),
+ *       r = sqrt((e_x e_x + e_y e_y) + e_z e_z) with e_k = max(p_k - lo_k, hi_k - p_k): the farthest corner of the node's box, so
+ *       every vertex of the node lies within r of p.  N, p, C and r are rounded to fp32 once, after these steps.
+ * Query, one thread per point.  Q1  lb2(node) = dot(e, e), e_k = max(max(lo_k - p_k, p_k - hi_k), 0).  Depth first (the child
+ *       with the smaller lb2 first, the left one among equals); a node is skipped only when lb2 > best, strictly; a leaf's faces
+ *       are measured by the field query's per-pair rule and a candidate replaces the best when (d2, face index) is
+ *       lexicographically smaller: face is the first minimum in the ORIGINAL face order, whatever the order of the walk.
+ *       dist = sqrtf(best); out_attr is interpolated once, on the winning face.  delta makes lb2 <= the computed d2 of every
+ *       face below the node (DESIGN.md "Mesh BVH": the computed closest point stays inside the inflated box).
+ *   Q2  wn: left first from the root, x = p_node - p, d2 = dot(x, x); the node is opened iff d2 <= (beta r) * (beta r): a leaf
+ *       then adds its faces' atan2 terms in sorted order, an inner node its children.  A node that is not opened adds
+ *       0.5 * ((dot(N, x) / d3 + tr / d3) - (3 xCx) / d5), d = sqrtf(d2), d3 = d2 d, d5 = d3 d2, tr = (C00 + C11) + C22,
+ *       xCx = dot(x, (dot(C0., x), dot(C1., x), dot(C2., x))).  wn = sum * (1 / 2 pi).  beta >= 0; the larger, the more nodes are
+ *       opened and the closer wn is to the exact sum (beta = +inf opens every node).
+ *
+ * primx_mesh_bvh_workspace: bytes of the tree of F faces (records, order, nodes, the build's float64 sums: at most 180 F + 10 KiB).
+ * primx_mesh_bvh_build, two passes over the same ws (16-byte aligned, any contents on entry of the first):
+ *   order == NULL: the key pass, B1 - B2 -> keys [F] int64.  A face with an index outside [0, V) gets code 0.  Nothing is read
+ *                  back and the host does not wait.
+ *   order != NULL: the tree pass, order [F] int32 = the argsort of the keys (keys may be NULL) -> the tree in ws.  A face index
+ *                  outside [0, V) or an entry of order outside [0, F) returns PRIMX_EINVAL (nothing is read out of bounds; that
+ *                  order is a permutation is not checked): the call synchronises the stream once, where it reads that check
+ *                  back - the one read-back of building and querying.  1 + log2(L) + 5 launches.
+ * primx_mesh_bvh_query: pts [n, 3], f [F, 3] and attr [V, C] as the tree pass saw them (C in 0 .. 16; C = 0: attr / out_attr
+ *   unused), bvh = the ws of a finished tree pass of the same F -> dist, face, wn [n], out_attr [n, C].  One launch, no
+ *   workspace of its own, nothing read back, no host synchronisation.  The point index is 64 bits wide.  n == 0 launches nothing.
+ * -------------------------------------------------------------------------------------------- */
+int primx_mesh_bvh_workspace(int F, int64_t* bytes);
+int primx_mesh_bvh_build(const float* v, const int* f, int V, int F, const int* order, int64_t* keys, void* ws, int64_t ws_bytes,
+                         void* stream);
+int primx_mesh_bvh_query(const float* pts, int64_t n, const int* f, int F, const float* attr, int C, const void* bvh,
+                         int64_t bvh_bytes, float beta, float* dist, int* face, float* wn, float* out_attr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
