@@ -155,6 +155,8 @@ SIGNATURES = {
     "primx_mesh_bvh_workspace": [_i, C.POINTER(_l)],
     "primx_mesh_bvh_build": [_p, _p, _i, _i, _p, _p, _p, _l, _p],
     "primx_mesh_bvh_query": [_p, _l, _p, _i, _p, _i, _p, _l, _f, _p, _p, _p, _p, _p],
+    "primx_mesh_bvh_raycast": [_p, _p, _l, _f, _f, _i, _p, _i, _p, _l, _p, _p, _p, _p],
+    "primx_mesh_bvh_visibility": [_p, _l, _p, _i, _f, _i, _p, _i, _p, _l, _p, _p],
 }
 _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_p}
 # An alternate build named by PRIMX_LIB (same-box A/B against another build) must speak the same ABI.  Version 21 changed the argument
@@ -165,7 +167,8 @@ _RESTYPES = {"primx_last_error": C.c_char_p, "primx_last_gemm_kernel": C.c_char_
 # symbol, which `load` finds out with hasattr.  A version-24 build ignores the kv_* tail of PrimxDitForwardFold that came with
 # primx_linear_heads_fold_pair (the host then projects K / V itself).  The normal map's three entry points joined version 35 the same
 # way but are listed with the number 35: under PRIMX_LIB an absent entry point of 35 is skipped like a probed one.  So did the ambient
-# occlusion's primx_texbake_occlusion, the two entry points of the quality metrics (metrics.py) and the three of the mesh BVH (fit.MeshBVH).
+# occlusion's primx_texbake_occlusion, the two entry points of the quality metrics (metrics.py), the three of the mesh BVH (fit.MeshBVH)
+# and the two of its ray queries (MeshBVH.raycast, MeshBVH.visibility).
 _PROBE = 0
 _SINCE: dict = {
     **dict.fromkeys(("primx_linear_f32out", "primx_row_stats", "primx_linear_gate_residual_fold", "primx_linear_heads_fold",
@@ -191,6 +194,7 @@ _SINCE: dict = {
     "primx_texbake_occlusion": 35,                                                               # ambient occlusion, the same way
     **dict.fromkeys(("primx_nearest_points", "primx_distance_stats"), 35),                       # metrics.py, the same way
     **dict.fromkeys(("primx_mesh_bvh_workspace", "primx_mesh_bvh_build", "primx_mesh_bvh_query"), 35),   # fit.MeshBVH, the same way
+    **dict.fromkeys(("primx_mesh_bvh_raycast", "primx_mesh_bvh_visibility"), 35),                # its ray queries, the same way
     **dict.fromkeys(("primx_material_sample",                                                    # a MeshField with a material
                      "primx_attention_ksplit_mode", "primx_attention_ksplit",                    # without them: attention never splits its keys
                      "primx_gemm_toq64_mode",                                                    # without it: to_q under the null skip on the 128-row tile

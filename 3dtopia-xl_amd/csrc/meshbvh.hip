@@ -12,6 +12,8 @@
 //           next (up while the node is the second child of its parent, then to the sibling: a count of trailing bits), so
 //           no thread keeps an array.  The distance walk visits the nearer child first and keeps, one bit per level, which
 //           child that was; the winding walk goes left first.
+//   rays:   one thread per ray, or per point with a table of directions ("Mesh rays" R1-R6; restatement: tests/meshray_numpy.py):
+//           the distance walk's way through the tree with the watertight ray / triangle test and the box test of meshray_pair.h.
 //
 // Every floating-point expression is evaluated as written (no contraction).
 #include <cmath>
@@ -26,6 +28,8 @@ namespace {
 #include "mesh_common.h"
 
 #include "meshfield_pair.h"
+
+#include "meshray_pair.h"
 
 constexpr int LEAF = 8;                  // faces per leaf
 constexpr int NODE_F4 = 6;               // float4 per node (96 bytes)
@@ -358,6 +362,91 @@ __global__ __launch_bounds__(THREADS) void bvh_query_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ rays ("Mesh rays", R1-R6)
+// The closest accepted record along one ray, or with `any` the first one met: the distance walk's way through the tree (no
+// stack: node and trail), the child whose interval starts nearer first, a node skipped only when ray_box refuses it.
+__device__ __forceinline__ void ray_walk(const Ray& q, float tmin, float tmax, bool any, const float4* __restrict__ recs,
+                                         const int* __restrict__ orig, const float4* __restrict__ nodes, int L, int F, float& bt,
+                                         int& bf, float& bv, float& bw) {
+    bt = tmax, bf = -1, bv = 0.0f, bw = 0.0f;
+    if (!q.ok) return;
+    unsigned node = 1, trail = 0;
+    while (true) {
+        const float4 q0 = nodes[(int64_t)NODE_F4 * node], q1 = nodes[(int64_t)NODE_F4 * node + 1];
+        bool descend = false;
+        float tn;
+        if (__float_as_int(q1.w) != 0 && ray_box(q, q0, q1, tmin, bt, tn)) {
+            if (node >= (unsigned)L) {
+                const int first = LEAF * (int)(node - (unsigned)L), cnt = min(LEAF, F - first);
+                for (int j = 0; j < cnt; ++j) {
+                    const Rec r = unpack(recs + (int64_t)4 * (first + j));
+                    float t, v, w;
+                    if (!ray_pair(q, r, tmin, tmax, t, v, w)) continue;
+                    const int of = orig[first + j];
+                    if (bf < 0 || t < bt || (t == bt && of < bf)) bt = t, bf = of, bv = v, bw = w;   // (t, face), lexicographic
+                }
+                if (any && bf >= 0) break;
+            } else {
+                descend = true;
+            }
+        }
+        if (descend) {
+            const float4* c = nodes + (int64_t)NODE_F4 * 2 * node;
+            const float4 l0 = c[0], l1 = c[1], r0 = c[NODE_F4], r1 = c[NODE_F4 + 1];
+            float tl, tr;
+            const bool hl = __float_as_int(l1.w) != 0 && ray_box(q, l0, l1, tmin, bt, tl);
+            const bool hr = __float_as_int(r1.w) != 0 && ray_box(q, r0, r1, tmin, bt, tr);
+            const unsigned right_first = hr && (!hl || tr < tl) ? 1u : 0u;
+            node = 2 * node + right_first;
+            trail = 2 * trail + right_first;
+        } else {
+            unsigned u = (node ^ trail) + 1;                 // up past every second child, then to the sibling
+            const int s = __builtin_ctz(u);
+            u >>= s;
+            if (u == 1) break;
+            trail >>= s;
+            node = u ^ trail;
+        }
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void bvh_raycast_kernel(const float* __restrict__ org, const float* __restrict__ dir, int64_t n,
+                                                              float tmin, float tmax, int any, const float4* __restrict__ recs,
+                                                              const int* __restrict__ orig, const float4* __restrict__ nodes, int L,
+                                                              int F, float* __restrict__ t, int* __restrict__ face,
+                                                              float* __restrict__ bary) {
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const Ray q = ray_setup(org[3 * i], org[3 * i + 1], org[3 * i + 2], dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+    float bt, bv, bw;
+    int bf;
+    ray_walk(q, tmin, tmax, any != 0, recs, orig, nodes, L, F, bt, bf, bv, bw);
+    t[i] = bf >= 0 ? bt : INFINITY;
+    face[i] = bf;
+    bary[2 * i] = bv, bary[2 * i + 1] = bw;
+}
+
+// one thread per point: an any-hit ray along each direction in turn, tmax = inf; the number that met nothing, up to `limit`
+__global__ __launch_bounds__(THREADS) void bvh_visibility_kernel(const float* __restrict__ pts, int64_t n,
+                                                                 const float* __restrict__ dirs, int D, float tmin, int limit,
+                                                                 const float4* __restrict__ recs, const int* __restrict__ orig,
+                                                                 const float4* __restrict__ nodes, int L, int F,
+                                                                 int* __restrict__ escapes) {
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
+    int esc = 0;
+    for (int k = 0; k < D; ++k) {
+        const Ray q = ray_setup(px, py, pz, dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
+        float bt, bv, bw;
+        int bf;
+        ray_walk(q, tmin, INFINITY, true, recs, orig, nodes, L, F, bt, bf, bv, bw);
+        if (bf < 0) ++esc;
+        if (limit > 0 && esc >= limit) break;
+    }
+    escapes[i] = esc;
+}
+
 int bounding_box(const float* v, int V, char* ws, const Layout& lay, hipStream_t st, const char* name) {
     int per = (V + BB_MAXB - 1) / BB_MAXB;
     if (per < BB_PER_BLOCK) per = BB_PER_BLOCK;
@@ -439,6 +528,50 @@ extern "C" int primx_mesh_bvh_query(const float* pts, int64_t n, const int* f, i
     hipLaunchKernelGGL(bvh_query_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, pts, n, (const float4*)(w + lay.recs),
                        (const int*)(w + lay.orig), (const float4*)(w + lay.nodes), lay.L, F, f, attr, C, beta, dist, face, wn,
                        out_attr);
+    PRIMX_CHECK_LAUNCH(name);
+    return PRIMX_OK;
+}
+
+extern "C" int primx_mesh_bvh_raycast(const float* org, const float* dir, int64_t n, float tmin, float tmax, int any_hit,
+                                      const int* f, int F, const void* bvh, int64_t bvh_bytes, float* t, int* face, float* bary,
+                                      void* stream) {
+    const char* name = "primx_mesh_bvh_raycast";
+    hipStream_t st = (hipStream_t)stream;
+    PRIMX_REQUIRE(f, "%s: null pointer", name);
+    PRIMX_REQUIRE(F >= 1 && F <= INT32_MAX / 4, "%s: F must lie in 1 .. (2^31 - 1) / 4 (got %d)", name, F);
+    PRIMX_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX * THREADS, "%s: n out of range", name);
+    PRIMX_REQUIRE(tmin <= tmax, "%s: tmin must not exceed tmax, and neither may be a NaN", name);
+    const Layout lay = layout(F);
+    PRIMX_REQUIRE(bvh && ((uintptr_t)bvh & 15) == 0 && bvh_bytes >= lay.total,
+                  "%s: the tree needs primx_mesh_bvh_workspace(F) = %lld bytes, 16-byte aligned", name, (long long)lay.total);
+    if (n == 0) return PRIMX_OK;
+    PRIMX_REQUIRE(org && dir && t && face && bary, "%s: null pointer", name);
+    const char* w = (const char*)bvh;
+    hipLaunchKernelGGL(bvh_raycast_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, org, dir, n, tmin, tmax, any_hit,
+                       (const float4*)(w + lay.recs), (const int*)(w + lay.orig), (const float4*)(w + lay.nodes), lay.L, F, t, face,
+                       bary);
+    PRIMX_CHECK_LAUNCH(name);
+    return PRIMX_OK;
+}
+
+extern "C" int primx_mesh_bvh_visibility(const float* pts, int64_t n, const float* dirs, int D, float tmin, int limit, const int* f,
+                                         int F, const void* bvh, int64_t bvh_bytes, int* escapes, void* stream) {
+    const char* name = "primx_mesh_bvh_visibility";
+    hipStream_t st = (hipStream_t)stream;
+    PRIMX_REQUIRE(f && dirs, "%s: null pointer", name);
+    PRIMX_REQUIRE(F >= 1 && F <= INT32_MAX / 4, "%s: F must lie in 1 .. (2^31 - 1) / 4 (got %d)", name, F);
+    PRIMX_REQUIRE(n >= 0 && n <= (int64_t)INT32_MAX * THREADS, "%s: n out of range", name);
+    PRIMX_REQUIRE(D >= 1 && D <= INT32_MAX / 3, "%s: D must be at least 1 (got %d)", name, D);
+    PRIMX_REQUIRE(limit >= 0, "%s: limit must be at least 0 (got %d)", name, limit);
+    PRIMX_REQUIRE(tmin <= INFINITY, "%s: tmin is a NaN", name);
+    const Layout lay = layout(F);
+    PRIMX_REQUIRE(bvh && ((uintptr_t)bvh & 15) == 0 && bvh_bytes >= lay.total,
+                  "%s: the tree needs primx_mesh_bvh_workspace(F) = %lld bytes, 16-byte aligned", name, (long long)lay.total);
+    if (n == 0) return PRIMX_OK;
+    PRIMX_REQUIRE(pts && escapes, "%s: null pointer", name);
+    const char* w = (const char*)bvh;
+    hipLaunchKernelGGL(bvh_visibility_kernel, dim3(nblocks(n, THREADS)), dim3(THREADS), 0, st, pts, n, dirs, D, tmin, limit,
+                       (const float4*)(w + lay.recs), (const int*)(w + lay.orig), (const float4*)(w + lay.nodes), lay.L, F, escapes);
     PRIMX_CHECK_LAUNCH(name);
     return PRIMX_OK;
 }

@@ -13,7 +13,8 @@ Kernels (csrc/meshfield.hip, rules in include/primx_hip.h "Primitive fitting"): 
 the faces: exact point-triangle distance, generalized winding number, attributes at the closest point),
 `primx_mesh_face_areas`, `primx_mesh_surface_points`, `primx_fps`; csrc/meshbvh.hip ("Mesh BVH"): `MeshBVH`, the same query
 through a bounding volume hierarchy (`accel="bvh"`: the same dist, face and attributes bit for bit, the winding number by a
-far-field expansion; `accel=None`, the default, is the brute-force call); csrc/material.hip ("Textured meshes"): `primx_material_sample`
+far-field expansion; `accel=None`, the default, is the brute-force call; `MeshBVH.raycast` and `MeshBVH.visibility` cast
+watertight rays through the same tree - "Mesh rays" - and `sign="visibility"` takes inside / outside from them); csrc/material.hip ("Textured meshes"): `primx_material_sample`
 (the glTF material of a `mesh.MaterialMesh` at the closest point).  Torch does the plumbing: the float64 inclusive sum of the
 areas (on the host, where it is sequential and therefore reproducible to the bit), the seeded uniforms (a CPU generator, as the
 sampler draws its noise), the normalisation and the assembly of `recon_param`.
@@ -86,7 +87,7 @@ def morton_order(x: torch.Tensor) -> torch.Tensor:
 
 class MeshBVH:
     """The bounding volume hierarchy of a triangle mesh (include/primx_hip.h "Mesh BVH"): built once, here, and reusable for any
-    number of `query` calls.  v [V, 3] float32, f [F, 3] int32 on a HIP device; face indices outside [0, V) raise (the one
+    number of `query`, `raycast` and `visibility` calls.  v [V, 3] float32, f [F, 3] int32 on a HIP device; face indices outside [0, V) raise (the one
     read-back of the tree: `query` has none and does not make the host wait).  The sort of the faces' Morton keys is torch's.
     `ws`: the `.ws` of a tree built earlier from the same v and f (a cached one): nothing is built or checked then."""
 
@@ -95,6 +96,7 @@ class MeshBVH:
         self.v, self.f = _mesh_args(v, f)
         V, F, dev = self.v.shape[0], self.f.shape[0], self.v.device
         self.layout = bvh_layout(F)
+        self._directions = {}                                    # K -> the Fibonacci sphere on the device (`visibility`)
         if ws is not None:
             if ws.dtype != torch.uint8 or ws.dim() != 1 or ws.numel() < self.layout["total"] or not ws.is_contiguous():
                 raise ValueError(f"ws must be the {self.layout['total']} bytes of a MeshBVH of {F} faces")
@@ -150,6 +152,97 @@ class MeshBVH:
                 back = lambda t: torch.empty_like(t).index_copy_(0, perm, t)   # noqa: E731
                 dist, face, wn, out = back(dist), back(face), back(wn), None if out is None else back(out)
         return dist, face, wn, out
+
+    def _rays(self, name, *pairs):
+        out = []
+        for label, t in pairs:
+            t = t.float().contiguous()
+            if t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError(f"{name}: {label} must be [n, 3], got {tuple(t.shape)}")
+            out.append(t)
+        return out
+
+    def raycast(self, origins: torch.Tensor, dirs: torch.Tensor, tmin: float = 0.0, tmax: float = float("inf"),
+                any_hit: bool = False, attr: Optional[torch.Tensor] = None):
+        """origins, dirs [n, 3] -> (t [n], face [n] int32, bary [n, 2], out_attr [n, C] or None): primx_mesh_bvh_raycast, the
+        closest hit of each ray o + t d with t in [tmin, tmax] (include/primx_hip.h "Mesh rays": the watertight test of Woop et
+        al. 2013, two-sided; d need not be normalised, t is in units of its length).  A miss - also a zero or non-finite ray -
+        has t = inf, face = -1 and bary = 0.  hit = a + bary[0] (b - a) + bary[1] (c - a) on face `face` (the lowest face index
+        among equal t).  `any_hit` stops at the first hit met: only face >= 0 means something then.  `attr` [V, C] is
+        interpolated here, in torch, as (a u + b v) + c w with u = (1 - v) - w, and is 0 on a miss.  One launch, nothing read
+        back."""
+        _need_cuda("MeshBVH.raycast", origins, dirs, attr)
+        o, d = self._rays("MeshBVH.raycast", ("origins", origins), ("dirs", dirs))
+        if o.shape != d.shape:
+            raise ValueError(f"origins and dirs must have the same shape, got {tuple(o.shape)} and {tuple(d.shape)}")
+        if not float(tmin) <= float(tmax):
+            raise ValueError(f"tmin must not exceed tmax, got {tmin} and {tmax}")
+        if attr is not None:
+            attr = attr.float().contiguous()
+            if attr.dim() != 2 or attr.shape[0] != self.v.shape[0]:
+                raise ValueError("attr must have one row per vertex")
+        n, F, dev = o.shape[0], self.f.shape[0], self.v.device
+        with torch.cuda.device(dev):
+            t = torch.empty(n, dtype=torch.float32, device=dev)
+            face = torch.empty(n, dtype=torch.int32, device=dev)
+            bary = torch.empty(n, 2, dtype=torch.float32, device=dev)
+            _lib.check(_lib.load().primx_mesh_bvh_raycast(
+                ops._dev(o, "origins", torch.float32) if n else None, ops._dev(d, "dirs", torch.float32) if n else None, n,
+                float(tmin), float(tmax), int(bool(any_hit)), ops._dev(self.f, "f", torch.int32), F, self.ws.data_ptr(),
+                self.ws.numel(), t.data_ptr() if n else None, face.data_ptr() if n else None, bary.data_ptr() if n else None,
+                ops._stream()), "primx_mesh_bvh_raycast")
+            out = None
+            if attr is not None:
+                hit = face >= 0
+                fa = self.f[face.clamp(min=0).long()].long()
+                v, w = bary[:, 0:1], bary[:, 1:2]
+                u = (1.0 - v) - w
+                out = (attr[fa[:, 0]] * u + attr[fa[:, 1]] * v) + attr[fa[:, 2]] * w
+                out = torch.where(hit[:, None], out, torch.zeros_like(out))
+        return t, face, bary, out
+
+    def visibility(self, x: torch.Tensor, directions=64, tmin: float = 0.0, limit: int = 0) -> torch.Tensor:
+        """x [n, 3] -> int32 [n]: how many of the rays from x along `directions` reach infinity without a hit
+        (primx_mesh_bvh_visibility; each ray stops at its first hit).  `directions`: an int K for the Fibonacci sphere of
+        `mesh.occlusion_directions(K)` (uploaded once per tree and K), or a tensor [D, 3] taken as given.  `limit` > 0 stops a
+        point once that many rays have escaped, so the count saturates there: a point outside usually costs one ray.  One
+        launch, nothing read back."""
+        _need_cuda("MeshBVH.visibility", x)
+        x, = self._rays("MeshBVH.visibility", ("x", x))
+        dev = self.v.device
+        if isinstance(directions, torch.Tensor):
+            _need_cuda("MeshBVH.visibility", directions)
+            dirs, = self._rays("MeshBVH.visibility", ("directions", directions))
+        else:
+            K = int(directions)
+            if K not in self._directions:
+                from . import mesh
+                self._directions[K] = mesh.occlusion_directions(K).to(dev).contiguous()
+            dirs = self._directions[K]
+        D, limit = dirs.shape[0], int(limit)
+        if D < 1 or limit < 0:
+            raise ValueError(f"visibility needs at least one direction and limit >= 0, got {D} and {limit}")
+        if not float(tmin) <= float("inf"):
+            raise ValueError(f"tmin must be a number, got {tmin}")
+        n, F = x.shape[0], self.f.shape[0]
+        with torch.cuda.device(dev):
+            esc = torch.empty(n, dtype=torch.int32, device=dev)
+            _lib.check(_lib.load().primx_mesh_bvh_visibility(
+                ops._dev(x, "x", torch.float32) if n else None, n, ops._dev(dirs, "directions", torch.float32), D, float(tmin), limit,
+                ops._dev(self.f, "f", torch.int32), F, self.ws.data_ptr(), self.ws.numel(), esc.data_ptr() if n else None,
+                ops._stream()), "primx_mesh_bvh_visibility")
+        return esc
+
+
+SIGNS = ("winding", "visibility")
+
+
+def _check_sign(sign, accel):
+    if sign not in SIGNS:
+        raise ValueError(f"sign must be one of {SIGNS}, got {sign!r}")
+    if sign == "visibility" and accel != "bvh":
+        raise ValueError('sign="visibility" casts rays through the tree: it needs accel="bvh"')
+    return sign
 
 
 def _check_accel(accel):
@@ -232,13 +325,26 @@ class MeshField:
     factors and textures there.  The tables and the texel blob are uploaded once, here.
 
     `accel="bvh"` builds a `MeshBVH` here and answers every query through it: sdf magnitude, face, tex and mat as without it, bit
-    for bit; the sign from the winding number approximated under `beta`.  `accel=None` is the brute-force query."""
+    for bit; the sign from the winding number approximated under `beta`.  `accel=None` is the brute-force query.
+
+    `sign="visibility"` (needs `accel="bvh"`) takes the sign from rays instead of the winding number, for meshes whose faces are
+    not oriented consistently (flipped faces, two-sided sheets, mirrored parts), where |wn| >= 0.5 fails outright: a point is
+    outside iff at least `min_escapes` of `sign_directions` fixed directions (`MeshBVH.visibility`) reach infinity without
+    hitting the mesh, sdf = dist there and -dist elsewhere; the dict gains 'escapes' (the count, saturated at `min_escapes`) and
+    keeps 'wn'.  What the rule does not do: an open sheet is outside everywhere, so its field is an unsigned distance; a deep
+    pocket narrower than the direction set resolves may count as inside; `min_escapes` > 1 closes pinholes in the surface at
+    the price of more such pockets.  The defaults (64 directions, 1 escape) are this project's choice and unmeasured on real
+    assets.  `sign="winding"`, the default, is the rule above and calls no ray kernel."""
 
     def __init__(self, v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None, accel=None,
-                 beta: float = BVH_BETA, sort_points: bool = False):
+                 beta: float = BVH_BETA, sort_points: bool = False, sign: str = "winding", sign_directions=64,
+                 min_escapes: int = 1):
         _need_cuda("mesh_field", v, f, attr)
         self.v, self.f = _mesh_args(v, f)
         self.accel, self.beta, self.sort_points = _check_accel(accel), float(beta), bool(sort_points)
+        self.sign, self.sign_directions, self.min_escapes = _check_sign(sign, accel), sign_directions, int(min_escapes)
+        if self.min_escapes < 1:
+            raise ValueError(f"min_escapes must be at least 1, got {min_escapes}")
         self.bvh = MeshBVH(self.v, self.f) if accel == "bvh" else None      # built once, for every chunk and refinement step
         self.material = None
         if material is not None:
@@ -262,20 +368,29 @@ class MeshField:
             dist, face, wn, a = mesh_field_query(x, self.v, self.f, self.attr)
         else:
             dist, face, wn, a = self.bvh.query(x, self.attr, self.beta, self.sort_points)
-        sdf = torch.where(wn.abs() >= 0.5, -dist, dist)[:, None]
+        escapes = None
+        if self.sign == "visibility":
+            escapes = self.bvh.visibility(x, self.sign_directions, limit=self.min_escapes)
+            sdf = torch.where(escapes >= self.min_escapes, dist, -dist)[:, None]
+        else:
+            sdf = torch.where(wn.abs() >= 0.5, -dist, dist)[:, None]
         if self.material is not None:
             a = material_sample(a[:, 0:2], a[:, 2:8], face, *self.material)
         if a is None:
             a = torch.zeros(x.shape[0], N_ATTR, dtype=torch.float32, device=dist.device)
         a = a.clip(0, 1)
-        return {"sdf": sdf, "tex": a[:, 0:3], "mat": a[:, 3:5], "face": face, "wn": wn}
+        out = {"sdf": sdf, "tex": a[:, 0:3], "mat": a[:, 3:5], "face": face, "wn": wn}
+        if escapes is not None:
+            out["escapes"] = escapes
+        return out
 
     __call__ = query
 
 
 def mesh_field(v: torch.Tensor, f: torch.Tensor, attr: Optional[torch.Tensor] = None, material=None, accel=None,
-               beta: float = BVH_BETA) -> MeshField:
-    return MeshField(v, f, attr, material, accel=accel, beta=beta)
+               beta: float = BVH_BETA, sign: str = "winding", sign_directions=64, min_escapes: int = 1) -> MeshField:
+    return MeshField(v, f, attr, material, accel=accel, beta=beta, sign=sign, sign_directions=sign_directions,
+                     min_escapes=min_escapes)
 
 
 @ops.on_input_device
@@ -385,7 +500,7 @@ def refine_points(srt: torch.Tensor, samples_per_prim: int, seed: int = 0) -> to
 
 def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, samples_per_prim: int = 256, seed: int = 0,
                       refine_srt: bool = False, weights=(1.0, 1.0, 1.0), lr_srt: Optional[float] = None, chunk: int = 1 << 20,
-                      accel=None, beta: float = BVH_BETA):
+                      accel=None, beta: float = BVH_BETA, sign: str = "winding", sign_directions=64, min_escapes: int = 1):
     """`steps` full-batch Adam steps on recon [P, 4 + 6 S^3] (fp32, HIP device) against `field.query` (a `MeshField`, or anything
     returning {'sdf' [n, 1], 'tex' [n, 3], 'mat' [n, 2]}) -> (recon', info).  `recon` itself is not modified.
 
@@ -400,13 +515,15 @@ def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, 
     'target'.  The gradient sums are atomic: the last bits differ from run to run.
 
     `field` may also be a mesh (anything `mesh_to_primitives` takes, already in the primitives' frame): the field is then built
-    here, with `accel` and `beta` as `MeshField` takes them.  A field that is given keeps its own."""
+    here, with `accel`, `beta`, `sign`, `sign_directions` and `min_escapes` as `MeshField` takes them.  A field that is given
+    keeps its own."""
     from . import primsdf
     _need_cuda("refine_primitives", recon)
     _check_accel(accel)
     if not hasattr(field, "query"):
         v, f, attr, material = _mesh_parts(field, recon.device)
-        field = MeshField(v, f, attr, material, accel=accel, beta=beta)
+        field = MeshField(v, f, attr, material, accel=accel, beta=beta, sign=sign, sign_directions=sign_directions,
+                          min_escapes=min_escapes)
     if recon.dim() != 2 or recon.dtype != torch.float32:
         raise ValueError("recon must be fp32 [P, 4 + 6 S^3]")
     P = recon.shape[0]
@@ -446,7 +563,8 @@ def refine_primitives(recon: torch.Tensor, field, steps: int, lr: float = 1e-3, 
 
 def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candidates: Optional[int] = None, seed: int = 0,
                        normalize: bool = True, extent: float = 0.9, device=None, chunk: int = 1 << 20, refine: int = 0,
-                       refine_kw: Optional[dict] = None, accel=None, beta: float = BVH_BETA):
+                       refine_kw: Optional[dict] = None, accel=None, beta: float = BVH_BETA, sign: str = "winding",
+                       sign_directions=64, min_escapes: int = 1):
     """mesh: a `mesh.TriMesh`, (v, f, albedo [V, 3], roughness [V], metallic [V]) or a `mesh.MaterialMesh` (e.g. from
     `mesh.read_glb`: colour and material come from its textures and factors) -> (recon_param [P, 4 + 6 S^3], info).
 
@@ -457,8 +575,12 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
     (`center`, `scale`: v' = (v - center) * scale), the candidates (`candidates`, `candidate_face`) and the chosen ones (`idx`).
     `refine=N` > 0 follows the initialisation with N steps of `refine_primitives(recon, field, N, **refine_kw)` against the
     normalised mesh's field (`info['refine']` is its info); 0 is the initialisation alone.  `accel="bvh"` answers the payload's
-    and the refinement's field queries through one `MeshBVH` of the normalised mesh (`MeshField(accel=, beta=)`)."""
+    and the refinement's field queries through one `MeshBVH` of the normalised mesh (`MeshField(accel=, beta=)`).
+    `sign="visibility"` (with `accel="bvh"`; `sign_directions`, `min_escapes`) takes inside / outside from rays through that tree
+    instead of the winding number, for meshes without a consistent orientation - `MeshField` says what the rule does and does not
+    do; the refinement runs against the same field."""
     _check_accel(accel)
+    _check_sign(sign, accel)
     if device is None:
         v0 = mesh[0] if isinstance(mesh, (tuple, list)) else mesh.v
         device = v0.device if isinstance(v0, torch.Tensor) and v0.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -478,7 +600,8 @@ def mesh_to_primitives(mesh, num_prims: int = 2048, prim_shape: int = 8, candida
         idx, nn = fps(cand, P, 0)
         pos = cand[idx.long()]
         x = (pos[:, None, :] + nn[:, None, None] * _local_grid(S, dev)[None]).reshape(-1, 3)
-        field = MeshField(v, f, attr, material, accel=accel, beta=beta)
+        field = MeshField(v, f, attr, material, accel=accel, beta=beta, sign=sign, sign_directions=sign_directions,
+                          min_escapes=min_escapes)
         parts = [field.query(x[lo:lo + chunk]) for lo in range(0, x.shape[0], chunk)]
         sdf = torch.cat([q["sdf"] for q in parts]).reshape(P, S ** 3)
         a = torch.cat([torch.cat([q["tex"], q["mat"]], 1) for q in parts]).reshape(P, S ** 3, N_ATTR)

@@ -61,6 +61,9 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="refinement steps after the initialisation (fit.refine_primitives)")
     ap.add_argument("--accel", choices=["bvh"], default=None,
                     help="answer the mesh's field queries through a BVH (fit.MeshBVH) instead of brute force over the faces")
+    ap.add_argument("--sign", choices=["winding", "visibility"], default="winding",
+                    help="inside / outside from the winding number, or (with --accel bvh) from rays through the BVH: for meshes "
+                    "whose faces are not oriented consistently (fit.MeshField)")
     ap.add_argument("--resolution", type=int, default=256)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--vae", default=None, help="VAE checkpoint (.pt with 'model_state_dict'); random weights when absent")
@@ -95,9 +98,9 @@ def main():
     else:
         mesh = timed("read_ply", lambda: pipeline.read_ply(path, device=dev))
     print(f"  V = {mesh.v.shape[0]}  F = {mesh.f.shape[0]}")
-    timed("mesh_to_primitives (first call)", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed, accel=a.accel))
+    timed("mesh_to_primitives (first call)", lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed, accel=a.accel, sign=a.sign))
     recon, info = timed("mesh_to_primitives" + (f" (accel={a.accel})" if a.accel else ""),
-                        lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed, accel=a.accel))
+                        lambda: pipeline.mesh_to_primitives(mesh, num_prims=a.prims, seed=a.seed, accel=a.accel, sign=a.sign))
     print(f"  recon_param {tuple(recon.shape)}  scale {float(recon[:, 0].min()):.4f} .. {float(recon[:, 0].max()):.4f}  "
           f"normalised by x{float(info['scale']):.4f}")
 
@@ -117,8 +120,8 @@ def main():
     report(field, "fitted")
     if a.refine > 0:
         from topia_xl_amd import fit
-        target = fit.MeshField(info["v"], info["f"], material=mesh, accel=a.accel) if is_glb else \
-            fit.MeshField(info["v"], info["f"], info["attr"], accel=a.accel)
+        target = fit.MeshField(info["v"], info["f"], material=mesh, accel=a.accel, sign=a.sign) if is_glb else \
+            fit.MeshField(info["v"], info["f"], info["attr"], accel=a.accel, sign=a.sign)
         fit.refine_primitives(recon, target, 1)                                       # (first call: loads the kernels)
         recon, rinfo = timed(f"refine_primitives, {a.refine} steps", lambda: fit.refine_primitives(recon, target, a.refine))
         print(f"  loss {rinfo['loss'][0]:.3e} -> {rinfo['loss'][-1]:.3e}")

@@ -1248,6 +1248,49 @@ int primx_mesh_bvh_build(const float* v, const int* f, int V, int F, const int* 
 int primx_mesh_bvh_query(const float* pts, int64_t n, const int* f, int F, const float* attr, int C, const void* bvh,
                          int64_t bvh_bytes, float beta, float* dist, int* face, float* wn, float* out_attr, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Mesh rays (csrc/meshbvh.hip, csrc/meshray_pair.h; added to ABI 35 without a new number: the two calls are purely additive).
+ * Rays against the tree of "Mesh BVH": the closest hit, and the visibility count that gives fit.MeshField a sign which does not
+ * depend on the faces' orientation.  The per-pair test is the watertight one of Woop, Benthin and Wald 2013 ("Watertight
+ * ray/triangle intersection"), two-sided.  tests/meshray_numpy.py restates R1-R6 in float32 (the kernels' bits) and float64.
+ * Every expression is evaluated as written, uncontracted, in fp32 unless float64 is named.
+ *
+ *   R1  The ray (o, d); d need not be normalised, t is in units of its length.  kz = the axis of d's largest |component| (the
+ *       first of equals), kx = kz + 1 and ky = kz + 2 (mod 3), exchanged when d[kz] < 0.  S = (d[kx] / d[kz], d[ky] / d[kz],
+ *       1 / d[kz]).  A ray with a non-finite coordinate of o or d, or a non-finite S.z (d = 0, or |d| below 2^-128), hits nothing.
+ *   R2  Per record of kind 0 (a record of another kind - zero area - is never hit), for each corner P in a, b, c:
+ *       Pz = P[kz] - o[kz], Px = (P[kx] - o[kx]) - S.x Pz, Py = (P[ky] - o[ky]) - S.y Pz.  The edge functions
+ *       U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.  If any of the three is exactly 0, all three are recomputed from
+ *       the fp32 Px, Py in float64 (the products are exact there): their signs are taken from the float64 values, which are then
+ *       rounded to fp32.  The pair is refused when one of them is < 0 and one is > 0 (two-sided: all >= 0 or all <= 0 passes).
+ *   R3  det = (U + V) + W; det == 0 or non-finite refuses.  t = ((U (S.z Az) + V (S.z Bz)) + W (S.z Cz)) / det, accepted iff
+ *       tmin <= t <= tmax (closed; a NaN is refused).  bary = (V / det, W / det): hit = a + bary.x ab + bary.y ac.
+ *   R4  Closest = the lexicographic minimum of (t, face index in the caller's numbering) over the accepted records.
+ *   R5  A node's inflated box [lo, hi] in the ray's frame: z0 = lo[kz] - o[kz], z1 = hi[kz] - o[kz], and x0, x1, y0, y1 likewise
+ *       for kx, ky; mx0 / mx1 = the min / max of S.x z0, S.x z1 (my0 / my1 with S.y; zl / zh with S.z);
+ *       tn = zl - m, tf = zh + m, m = 2^-20 max(|zl|, |zh|).  The node is skipped iff x0 - mx1 > 0, x1 - mx0 < 0, y0 - my1 > 0,
+ *       y1 - my0 < 0 (the box's shadow along the ray misses the origin: the slab test of the sheared frame), tf < tmin, or
+ *       tn > the best t so far, strictly.  A zero component of d needs no rule of its own: S.x = 0 makes the products 0 and the
+ *       test lo <= o <= hi on that axis; a NaN keeps the node.  The test is conservative with respect to R2 - R3: rounding is
+ *       monotone, so every corner's Px lies in [x0 - mx1, x1 - mx0] as computed, an accepted pair has 0 inside its Px and Py
+ *       ranges exactly, and its t within 7 x 2^-24 max(|zl|, |zh|) of [zl, zh] (DESIGN.md "Mesh rays").  The child whose tn is
+ *       smaller is visited first (the left one among equals, and when the right one is skipped).
+ *   R6  Visibility of a point p: rays (p, dirs[k]), k = 0 .. D - 1 in that order, tmax = +inf, each stopped at the first accepted
+ *       record; escapes = how many were accepted by nothing.  limit > 0 stops at escapes == limit.
+ *
+ * primx_mesh_bvh_raycast: org, dir [n, 3], f [F, 3] (not read: the tree holds the faces), bvh = the ws of a finished tree pass of
+ *   the same F -> t [n] (+inf on a miss), face [n] (-1 on a miss), bary [n, 2] (0, 0 on a miss).  any_hit != 0 stops each ray at
+ *   the first accepted record: only face >= 0 against face == -1 is contractual then.  tmin <= tmax (tmax may be +inf).  One
+ *   thread per ray, the ray index 64 bits wide; one launch, no workspace, nothing read back, no host synchronisation; n == 0
+ *   launches nothing.
+ * primx_mesh_bvh_visibility: pts [n, 3], dirs [D, 3] (device memory, D >= 1), limit >= 0 -> escapes [n] int32 (R6).  One thread
+ *   per point; one launch, no atomics, no workspace, nothing read back, no host synchronisation.
+ * -------------------------------------------------------------------------------------------- */
+int primx_mesh_bvh_raycast(const float* org, const float* dir, int64_t n, float tmin, float tmax, int any_hit, const int* f, int F,
+                           const void* bvh, int64_t bvh_bytes, float* t, int* face, float* bary, void* stream);
+int primx_mesh_bvh_visibility(const float* pts, int64_t n, const float* dirs, int D, float tmin, int limit, const int* f, int F,
+                              const void* bvh, int64_t bvh_bytes, int* escapes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
